@@ -10,7 +10,11 @@ per GPU, gradients all-reduced over RCCL).
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`, one rank per GPU,
     backend nccl = RCCL); under torchrun (RANK / LOCAL_RANK / WORLD_SIZE set by the launcher) it is one of the ranks.
 
-Prints ONE JSON line on rank 0 (see the driver contract) with two extra objects:
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 (see the driver contract):
+`value` = tile pairs / s over the K timed steps, `ms_per_step` = the time of one of them.
+    --dump-outputs DIR   also writes what the last timed step returned to its caller (the loss scalars and the change map) as
+                         DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be compared
+    --full               also runs the passes that take runs of their own and adds their objects to the line:
   roofline     -- the MFMA kernel family with the largest share of the step (today: the batched
                   GEMMs of the Winograd F(4x4,3x3) layers), timed with HIP events on the launch
                   stream in a second, profiled pass: executed FLOPs / event time against the peak
@@ -22,7 +26,7 @@ Prints ONE JSON line on rank 0 (see the driver contract) with two extra objects:
   cpu_baseline -- the CPU oracle (port of the reference's step on stock torch CPU ops)
                   timed on this box's host cores on a bounded sample (rank 0, N=1 only)
 `config.arithmetic` is generated from the library's switch state (fcd_conv_wino_split_set /
-fcd_conv_wgrad_split_set), and `fp32_mfma_only` is the same step with BOTH of them off: every
+fcd_conv_wgrad_split_set), and `fp32_mfma_only` (--full) is the same step with BOTH of them off: every
 matrix instruction of the step on the fp32 pipe.
 """
 import argparse
@@ -421,6 +425,32 @@ def latest_traffic_file():
     return files[-1] if files else None
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(dirpath, out, budget=DUMP_BUDGET_BYTES):
+    """Write what the last timed step returned to its caller (the step's dict: the loss scalars and the change map) as
+    ``dirpath/<name>.npy``, float32 (float64 tensors stay float64), at most ``budget`` bytes of files in all.  An array over its share of
+    the budget is written as a fixed sample of its flattened elements (indices drawn once from RandomState(0), ascending), so
+    two builds run with the same arguments write the same elements."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    arrs = {}
+    for k, v in out.items():
+        v = v.detach()
+        arrs[k] = v.to(torch.float64 if v.dtype == torch.float64 else torch.float32).cpu().numpy()
+    budget -= 128 * len(arrs)                                  # the .npy headers
+    if sum(a.nbytes for a in arrs.values()) > budget:
+        share = budget // len(arrs)
+        for k, a in arrs.items():
+            if a.nbytes > share:
+                idx = np.sort(np.random.RandomState(0).choice(a.size, share // a.itemsize, replace=False))
+                arrs[k] = a.reshape(-1)[idx]
+    for k, a in arrs.items():
+        np.save(os.path.join(dirpath, '%s.npy' % k), a)
+    return sorted(arrs)
+
+
 def _flush_c_stdio():
     import ctypes
     try:
@@ -441,9 +471,14 @@ def main():
     ap.add_argument('--batch', type=int, default=None, help='tile pairs per GPU per step (default: per workload)')
     ap.add_argument('--bands', type=int, default=None)
     ap.add_argument('--size', type=int, default=None)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-prof', action='store_true', help='skip the second (profiled) pass')
-    ap.add_argument('--no-alt', action='store_true', help='skip the extra pass with the Winograd GEMMs on the fp32 matrix pipe')
+    ap.add_argument('--full', action='store_true', help='after the headline also run the passes that take runs of their own: the fp32-pipe '
+                    'pass (fp32_mfma_only), the profiled pass (roofline, kernel_families, winograd, whole_step, --layers-md) and the CPU '
+                    'oracle baseline (cpu_baseline); without it: set up, warm up, time the steps, print the line')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='after the timed steps write what the last one returned '
+                    '(loss scalars, change map) as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU oracle baseline')
+    ap.add_argument('--no-prof', action='store_true', help='with --full: skip the second (profiled) pass')
+    ap.add_argument('--no-alt', action='store_true', help='with --full: skip the extra pass with the Winograd GEMMs on the fp32 matrix pipe')
     ap.add_argument('--prof-steps', type=int, default=3, help='steps of the profiled pass (HIP events around every launch)')
     ap.add_argument('--layers-md', default=None, help='write per-layer tables of the profiled pass to this markdown file')
     ap.add_argument('--no-throttle', action='store_true', help='switch LAUNCH_WINDOW=0: let the host run ahead until the hardware queue is full (it then '
@@ -453,6 +488,10 @@ def main():
     ap.add_argument('--backend', default='nccl', help="torch.distributed backend: 'nccl' (= RCCL over xGMI); "
                     "'gloo' only for functional tests of the multi-rank path on a single-GPU box")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if args.layers_md and (not args.full or args.no_prof):
+        ap.error('--layers-md is written by the profiled pass: add --full (without --no-prof)')
     _, d_bands, d_size, d_batch, wl_desc = WORKLOADS[args.workload]
     args.bands = args.bands or d_bands
     args.size = args.size or d_size
@@ -509,6 +548,7 @@ def main():
     dt = time.perf_counter() - t0
     cpu_all = time.process_time() - cpu0
     losses = {k: float(v.detach()) for k, v in out.items() if v.dim() == 0}
+    dumped = dump_outputs(args.dump_outputs, out) if (args.dump_outputs and rank == 0) else None
     host = {'host_cpu_ms_per_step': 1e3 * cpu_queued / args.steps,
             'host_cpu_ms_per_step_python_thread': 1e3 * thr_queued / args.steps,
             'host_wall_ms_per_step_until_queued': 1e3 * t_queued / args.steps,
@@ -530,7 +570,7 @@ def main():
     #      split-bf16 one: reported next to `value`, never as `value`
     alt = None
     pipes = {'wino_split': int(_lib.lib.fcd_conv_wino_split_set(-1) != 0), 'wgrad_split': int(_lib.lib.fcd_conv_wgrad_split_set(-1) != 0)}
-    if not args.no_alt and (pipes['wino_split'] or pipes['wgrad_split']):
+    if args.full and not args.no_alt and (pipes['wino_split'] or pipes['wgrad_split']):
         _lib.lib.fcd_conv_wino_split_set(0)
         _lib.lib.fcd_conv_wgrad_split_set(0)
         ksteps = max(1, min(args.steps, 3))
@@ -554,7 +594,7 @@ def main():
                'value': args.batch * n_gpus * ksteps / dta, 'unit': 'tile-pairs/s', 'ms_per_step': 1e3 * dta / ksteps, 'steps': ksteps}
     # ---- profiled pass (not part of `value`): every launch bracketed by HIP events on its stream
     prof, detail, dt_prof, psteps = {}, [], None, 0
-    if not args.no_prof:
+    if args.full and not args.no_prof:
         psteps = max(1, min(args.steps, args.prof_steps))
         step()                                                 # (re-pack after the fp32-pipe pass, outside the profiled region)
         _lib.prof_read(reset=True)
@@ -591,6 +631,7 @@ def main():
                                          if forced else 'none (1 rank)'),
                        'grad_exchange_last_step': exch},
             'losses_last_step': losses,
+            'full': bool(args.full), 'dumped_outputs': dumped,
             'peak_memory_bytes': {'allocated': int(torch.cuda.max_memory_allocated(dev)), 'reserved': int(torch.cuda.max_memory_reserved(dev)),
                                   'note': 'torch caching allocator, this rank, whole run (all passes); of 288 GB HBM3E'},
             'launch': 'launch by launch from Python (ctypes + autograd engine)',
@@ -701,7 +742,7 @@ def main():
                                  'profiled_ms_per_step': 1e3 * dt_prof / psteps,
                                  'note': 'value / ms_per_step are timed with the per-launch events OFF; the roofline and '
                                          'kernel_families numbers come from a second pass of %d step(s) with them on' % psteps}
-        if n_gpus == 1 and not args.no_cpu_baseline and args.workload == 'rsss':
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline and args.workload == 'rsss':
             res['cpu_baseline'] = cpu_baseline(args)
     # the JSON line is the LAST thing on stdout: RCCL / Gloo write their banners through C stdio, which -- redirected to a file or a
     # pipe -- is block-buffered and would otherwise come out at exit, behind the line.  Every rank flushes, then rank 0 prints.

@@ -61,6 +61,29 @@ def test_arithmetic_text_follows_the_switches():
     assert bench.check_result_consistency(res) == ['config.arithmetic does not describe config.pipes']
 
 
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    """--dump-outputs: one float32 / float64 .npy per entry of the step's result; over the budget an array becomes the same
+    fixed sample of its elements on every call."""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(3)
+    out = {'s_loss': torch.tensor(1.5, requires_grad=True), 'd64': torch.arange(4, dtype=torch.float64),
+           'cmap': torch.rand(2, 1, 64, 64, generator=g)}
+    assert bench.dump_outputs(str(tmp_path / 'a'), out) == ['cmap', 'd64', 's_loss']
+    a = {k: np.load(str(tmp_path / 'a' / (k + '.npy'))) for k in out}
+    assert a['s_loss'].dtype == np.float32 and a['s_loss'].shape == () and float(a['s_loss']) == 1.5
+    assert a['d64'].dtype == np.float64 and a['cmap'].dtype == np.float32
+    assert np.array_equal(a['cmap'], out['cmap'].numpy())
+    # a budget of 3 x 1024 bytes: the 32 KiB map is cut to its share, 224 sampled elements, the small entries stay whole
+    for d in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / d), out, budget=3 * 1024)
+    b, c = (np.load(str(tmp_path / d / 'cmap.npy')) for d in ('b', 'c'))
+    assert b.shape == (224,) and np.array_equal(b, c) and np.isin(b, a['cmap']).all()
+    assert sum(os.path.getsize(str(p)) for p in (tmp_path / 'b').iterdir()) <= 3 * 1024
+    assert np.array_equal(np.load(str(tmp_path / 'b' / 'd64.npy')), a['d64'])
+
+
 @pytest.mark.parametrize('path', sorted(glob.glob(os.path.join(ROOT, 'profiles', 'r06_bench*.json'))) or [None])
 def test_committed_round6_lines_are_self_consistent(path):
     if path is None:
