@@ -103,55 +103,43 @@ def _shared(t):
     return t
 
 
-def packed_weight(weight, mode):
-    """Packed GEMM-A layout of ``weight`` (mode 0 forward / 1 data-grad), cached on
-    the tensor object and keyed by its version counter.  fcd optimizers update
-    parameters outside autograd's view and call :func:`invalidate_packs`."""
+def _cached_pack(weight, key, elems, pack):
+    """The float32 buffer derived from ``weight`` under ``key``, cached on the tensor object (``weight._fcd_pack[key] =
+    (version, buffer)``) and rebuilt when the weight's version counter or device has moved: ``elems()`` floats, filled by
+    ``pack(w, buffer)`` from the detached contiguous weight.  fcd optimizers update parameters outside autograd's view and
+    call :func:`invalidate_packs` / :func:`refresh_packs`."""
     cache = weight.__dict__.setdefault('_fcd_pack', {})
     ver = weight._version
-    hit = cache.get(mode)
-    if hit is not None and hit[0] == ver and hit[1].device == weight.device:
-        return _shared(hit[1])
-    K, C, R, S = weight.shape
-    n = lib.fcd_conv_packed_elems(K, C, R, S, mode)
-    wp = torch.empty(n, dtype=torch.float32, device=weight.device)
-    w = weight.detach().contiguous()
-    check(lib.fcd_conv_pack_weights(_p(w), _p(wp), K, C, R, S, mode, _stream()), 'fcd_conv_pack_weights')
-    cache[mode] = (ver, wp)
-    return _shared(wp)
+    hit = cache.get(key)
+    if hit is None or hit[0] != ver or hit[1].device != weight.device:
+        buf = torch.empty(elems(), dtype=torch.float32, device=weight.device)
+        pack(weight.detach().contiguous(), buf)
+        hit = cache[key] = (ver, buf)
+    return _shared(hit[1])
+
+
+def packed_weight(weight, mode):
+    """Packed GEMM-A layout of ``weight`` (mode 0 forward / 1 data-grad), see :func:`_cached_pack`."""
+    def pack(w, wp):
+        K, C, R, S = w.shape
+        check(lib.fcd_conv_pack_weights(_p(w), _p(wp), K, C, R, S, mode, _stream()), 'fcd_conv_pack_weights')
+    return _cached_pack(weight, mode, lambda: lib.fcd_conv_packed_elems(*weight.shape, mode), pack)
 
 
 def wino_weight(weight, mode, m):
     """Winograd-transformed filters (fcd_conv_wino_pack), cached like :func:`packed_weight`."""
-    cache = weight.__dict__.setdefault('_fcd_pack', {})
-    ver = weight._version
+    def pack(w, U):
+        check(lib.fcd_conv_wino_pack(_p(w), _p(U), *w.shape[:2], mode, m, _stream()), 'fcd_conv_wino_pack')
     key = ('wino', mode, m, lib.fcd_conv_wino_split_set(-1) != 0)      # the pack writes fp32 U or its bf16 planes
-    hit = cache.get(key)
-    if hit is not None and hit[0] == ver and hit[1].device == weight.device:
-        return _shared(hit[1])
-    K, C = weight.shape[:2]
-    U = torch.empty(lib.fcd_conv_wino_filter_elems(K, C, mode, m), dtype=torch.float32, device=weight.device)
-    w = weight.detach().contiguous()
-    check(lib.fcd_conv_wino_pack(_p(w), _p(U), K, C, mode, m, _stream()), 'fcd_conv_wino_pack')
-    cache[key] = (ver, U)
-    return _shared(U)
+    return _cached_pack(weight, key, lambda: lib.fcd_conv_wino_filter_elems(*weight.shape[:2], mode, m), pack)
 
 
 def wino2_weight(weight, mode):
     """Filters transformed and packed for the fused F(2x2,3x3) kernel (fcd_conv_wino2_pack), cached like
     :func:`packed_weight`."""
-    cache = weight.__dict__.setdefault('_fcd_pack', {})
-    ver = weight._version
-    key = ('wino2', mode)
-    hit = cache.get(key)
-    if hit is not None and hit[0] == ver and hit[1].device == weight.device:
-        return _shared(hit[1])
-    K, C = weight.shape[:2]
-    U = torch.empty(lib.fcd_conv_wino2_filter_elems(K, C, mode), dtype=torch.float32, device=weight.device)
-    w = weight.detach().contiguous()
-    check(lib.fcd_conv_wino2_pack(_p(w), _p(U), K, C, mode, _stream()), 'fcd_conv_wino2_pack')
-    cache[key] = (ver, U)
-    return _shared(U)
+    def pack(w, U):
+        check(lib.fcd_conv_wino2_pack(_p(w), _p(U), *w.shape[:2], mode, _stream()), 'fcd_conv_wino2_pack')
+    return _cached_pack(weight, ('wino2', mode), lambda: lib.fcd_conv_wino2_filter_elems(*weight.shape[:2], mode), pack)
 
 
 def _bn_part(d, groups, relu, device):
@@ -165,10 +153,19 @@ def _bn_part(d, groups, relu, device):
 
 def _tag_bn(y, d, part, groups):
     if part is not None:
-        # the sums describe y AS THE KERNEL WROTE IT: the tag carries y's storage and version, and bn_act ignores it after any
+        # the sums describe y AS THE KERNEL WROTE IT: the tag carries y's storage and version, and _bn_parts ignores it after any
         # in-place edit of y (add_, a fused residual, a user hook) instead of normalising with stale statistics
         y._fcd_bn = (part, int(lib.fcd_conv_wino_bn_split(ctypes.byref(d), int(groups))), int(groups), y.data_ptr(), y._version)
     return y
+
+
+def _bn_parts(z, groups):
+    """``(buffer, split)`` of the partial sums :func:`_tag_bn` left on ``z`` for a BatchNorm over ``groups`` sample groups, or None:
+    no tag, a tag for other storage or an earlier version of z (see :func:`_tag_bn`), another grouping, or no sums."""
+    tag = getattr(z, '_fcd_bn', None)
+    if tag is None or tag[3] != z.data_ptr() or tag[4] != z._version or tag[2] != groups or tag[1] <= 0:
+        return None
+    return tag[0], tag[1]
 
 
 def _keepv(d, want_dw, device):
@@ -210,16 +207,9 @@ def _fwd_conv(d, x, weight, bias, y, relu, pool_y=None, code=None, v_keep=None, 
 
 def s2_weight(weight):
     """Filters packed for the sub-pixel data gradient of a stride-2 layer (fcd_conv_s2_dgrad_pack), cached."""
-    cache = weight.__dict__.setdefault('_fcd_pack', {})
-    ver = weight._version
-    hit = cache.get('s2')
-    if hit is not None and hit[0] == ver and hit[1].device == weight.device:
-        return _shared(hit[1])
-    K, C = weight.shape[:2]
-    wp = torch.empty(lib.fcd_conv_s2_dgrad_packed_elems(K, C), dtype=torch.float32, device=weight.device)
-    check(lib.fcd_conv_s2_dgrad_pack(_p(weight.detach().contiguous()), _p(wp), K, C, _stream()), 'fcd_conv_s2_dgrad_pack')
-    cache['s2'] = (ver, wp)
-    return _shared(wp)
+    def pack(w, wp):
+        check(lib.fcd_conv_s2_dgrad_pack(_p(w), _p(wp), *w.shape[:2], _stream()), 'fcd_conv_s2_dgrad_pack')
+    return _cached_pack(weight, 's2', lambda: lib.fcd_conv_s2_dgrad_packed_elems(*weight.shape[:2]), pack)
 
 
 def _bwd_data_conv(d, dy, weight, dx, yrelu=None, code=None):
@@ -335,6 +325,50 @@ def _channel_sum(t, mask, N, C, HW):
     return out
 
 
+def _ptr_list(ptrs):
+    return (ctypes.c_void_p * len(ptrs))(*ptrs)
+
+
+def _pair_cat_geom(fshape, ushape, wshape):
+    """``(d, chans, half)`` of the virtual ``cat([f2n[:n], f2n[n:], up], dim=1)`` in front of a 3x3 / stride-1 / pad-1 layer:
+    its descriptor, the channel counts of the three sources and the byte offset of the second temporal half inside ``f2n``."""
+    n, cu, H, W = ushape
+    c = fshape[1]
+    return _desc((n, 2 * c + cu, H, W), wshape, 1, 1), (ctypes.c_int * 3)(c, c, cu), n * c * H * W * 4
+
+
+def _pair_cat_ptrs(f, u, half):
+    """The three source (or gradient) pointers of :func:`_pair_cat_geom`'s concatenation."""
+    return _ptr_list([f.data_ptr(), f.data_ptr() + half, u.data_ptr()])
+
+
+def _weight_bias_grads(d, dy, yrelu, weight, bias, want_dw, want_db, x=None, vk=None, cat=None):
+    """``(dw, db)`` of a convolution layer, each None when not wanted.  With a weight gradient the bias's channel sums come
+    out of the dy re-layout pass of the same launch: from the forward pass's transformed input ``vk`` when it was kept, else
+    from the sources ``cat = (f2n, up, chans, half)`` of a pair concatenation, else from ``x``; a bias gradient alone is a
+    channel sum over (ReLU-gated) dy."""
+    dw = db = None
+    if want_dw:
+        dw = _grad_out(weight, weight.shape, dy.device)
+        if want_db:
+            db = _grad_out(bias, (d.K,), dy.device)
+        ws = _ws(lib.fcd_conv2d_bwd_weight_ws_bytes(ctypes.byref(d)), dy.device)
+        if vk is not None:
+            check(lib.fcd_conv2d_bwd_weight_bias_v(ctypes.byref(d), _p(vk), _p(dy), _p(yrelu), _p(dw), _p(db), _p(ws),
+                                                   ws.numel(), _stream()), 'fcd_conv2d_bwd_weight_bias_v')
+        elif cat is not None:
+            f2n, up, chans, half = cat
+            check(lib.fcd_conv2d_bwd_weight_bias_cat(ctypes.byref(d), _pair_cat_ptrs(f2n, up, half), chans, 3, _p(dy), _p(yrelu),
+                                                     _p(dw), _p(db), _p(ws), ws.numel(), _stream()),
+                  'fcd_conv2d_bwd_weight_bias_cat')
+        else:
+            check(lib.fcd_conv2d_bwd_weight_bias(ctypes.byref(d), _p(x), _p(dy), _p(yrelu), _p(dw), _p(db), _p(ws),
+                                                 ws.numel(), _stream()), 'fcd_conv2d_bwd_weight_bias')
+    elif want_db:
+        db = _channel_sum(dy, yrelu, d.N, d.K, d.P * d.Q)
+    return dw, db
+
+
 class _Conv2d(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, stride, pad, relu, bn_part=None, bn_groups=0):
@@ -377,7 +411,7 @@ class _Conv2d(torch.autograd.Function):
         stride, pad, has_bias, xshape = ctx.geom
         dy = _dev(dy, 'conv grad')
         d = _desc(xshape, weight.shape, stride, pad)
-        dx = dw = db = None
+        dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(xshape, dtype=torch.float32, device=dy.device)
             if bits is not None:
@@ -389,25 +423,9 @@ class _Conv2d(torch.autograd.Function):
                                                         _p(ws), ws.numel(), _stream()), 'fcd_conv2d_bwd_data_wino_bits')
             else:
                 _bwd_data_conv(d, dy, weight, dx, yrelu=yrelu)
-        want_db = has_bias and ctx.needs_input_grad[2]
-        if ctx.needs_input_grad[1]:
-            dw = _grad_out(weight, weight.shape, dy.device)
-            if want_db:        # channel sums come out of the dy re-layout pass of the weight gradient
-                db = _grad_out(ctx.bias_param, (d.K,), dy.device)
-            ws = _ws(lib.fcd_conv2d_bwd_weight_ws_bytes(ctypes.byref(d)), dy.device)
-            if vk is not None:
-                check(lib.fcd_conv2d_bwd_weight_bias_v(ctypes.byref(d), _p(vk), _p(dy), _p(yrelu), _p(dw), _p(db), _p(ws),
-                                                       ws.numel(), _stream()), 'fcd_conv2d_bwd_weight_bias_v')
-            else:
-                check(lib.fcd_conv2d_bwd_weight_bias(ctypes.byref(d), _p(x), _p(dy), _p(yrelu), _p(dw), _p(db), _p(ws),
-                                                     ws.numel(), _stream()), 'fcd_conv2d_bwd_weight_bias')
-        elif want_db:
-            db = _channel_sum(dy, yrelu, d.N, d.K, d.P * d.Q)
+        dw, db = _weight_bias_grads(d, dy, yrelu, weight, ctx.bias_param, ctx.needs_input_grad[1],
+                                    has_bias and ctx.needs_input_grad[2], x=x, vk=vk)
         return dx, dw, db, None, None, None, None, None
-
-
-def _ptr_list(ptrs):
-    return (ctypes.c_void_p * len(ptrs))(*ptrs)
 
 
 class _ConvPairCat(torch.autograd.Function):
@@ -420,19 +438,14 @@ class _ConvPairCat(torch.autograd.Function):
     @staticmethod
     def forward(ctx, f2n, up, weight, bias, relu, bn_part=None, bn_groups=0):
         f2n, up = _dev(f2n, 'skip pair'), _dev(up, 'upsampled input')
-        n, cu, H, W = up.shape
-        c = f2n.shape[1]
-        d = _desc((n, 2 * c + cu, H, W), weight.shape, 1, 1)
+        d, chans, half = _pair_cat_geom(f2n.shape, up.shape, weight.shape)
         y = torch.empty((d.N, d.K, d.P, d.Q), dtype=torch.float32, device=up.device)
-        half = n * c * H * W * 4
-        srcs = _ptr_list([f2n.data_ptr(), f2n.data_ptr() + half, up.data_ptr()])
-        chans = (ctypes.c_int * 3)(c, c, cu)
         ws = _ws(lib.fcd_conv_wino_ws_bytes(ctypes.byref(d), 0), up.device)
         b = _dev(bias, 'conv bias') if bias is not None else None
         vk = _keepv(d, ctx.needs_input_grad[2], up.device)
-        check(lib.fcd_conv2d_fwd_wino_cat_x(ctypes.byref(d), srcs, chans, 3, _p(wino_weight(weight, 0, 4)), _p(b), _p(y),
-                                            1 if relu else 0, _p(ws), ws.numel(), _extras(vk, bn_part, bn_groups), _stream()),
-              'fcd_conv2d_fwd_wino_cat')
+        check(lib.fcd_conv2d_fwd_wino_cat_x(ctypes.byref(d), _pair_cat_ptrs(f2n, up, half), chans, 3, _p(wino_weight(weight, 0, 4)),
+                                            _p(b), _p(y), 1 if relu else 0, _p(ws), ws.numel(), _extras(vk, bn_part, bn_groups),
+                                            _stream()), 'fcd_conv2d_fwd_wino_cat')
         keep_x = weight.requires_grad and vk is None
         ctx.save_for_backward(f2n if keep_x else None, up if keep_x else None, weight, y if relu else None, vk)
         ctx.geom = (tuple(f2n.shape), tuple(up.shape), bias is not None)
@@ -444,35 +457,17 @@ class _ConvPairCat(torch.autograd.Function):
         f2n, up, weight, yrelu, vk = ctx.saved_tensors
         fshape, ushape, has_bias = ctx.geom
         dy = _dev(dy, 'conv grad')
-        n, cu, H, W = ushape
-        c = fshape[1]
-        d = _desc((n, 2 * c + cu, H, W), weight.shape, 1, 1)
-        chans = (ctypes.c_int * 3)(c, c, cu)
-        half = n * c * H * W * 4
-        df = du = dw = db = None
+        d, chans, half = _pair_cat_geom(fshape, ushape, weight.shape)
+        df = du = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             df = torch.empty(fshape, dtype=torch.float32, device=dy.device)
             du = torch.empty(ushape, dtype=torch.float32, device=dy.device)
             ws = _ws(lib.fcd_conv_wino_ws_bytes(ctypes.byref(d), 1), dy.device)
             check(lib.fcd_conv2d_bwd_data_wino_cat(ctypes.byref(d), _p(dy), _p(yrelu), _p(wino_weight(weight, 1, 4)),
-                                                   _ptr_list([df.data_ptr(), df.data_ptr() + half, du.data_ptr()]), chans, 3,
-                                                   _p(ws), ws.numel(), _stream()), 'fcd_conv2d_bwd_data_wino_cat')
-        want_db = has_bias and ctx.needs_input_grad[3]
-        if ctx.needs_input_grad[2]:
-            dw = _grad_out(weight, weight.shape, dy.device)
-            if want_db:
-                db = _grad_out(ctx.bias_param, (d.K,), dy.device)
-            ws = _ws(lib.fcd_conv2d_bwd_weight_ws_bytes(ctypes.byref(d)), dy.device)
-            if vk is not None:
-                check(lib.fcd_conv2d_bwd_weight_bias_v(ctypes.byref(d), _p(vk), _p(dy), _p(yrelu), _p(dw), _p(db), _p(ws),
-                                                       ws.numel(), _stream()), 'fcd_conv2d_bwd_weight_bias_v')
-            else:
-                check(lib.fcd_conv2d_bwd_weight_bias_cat(ctypes.byref(d), _ptr_list([f2n.data_ptr(), f2n.data_ptr() + half,
-                                                                                      up.data_ptr()]), chans, 3, _p(dy), _p(yrelu),
-                                                         _p(dw), _p(db), _p(ws), ws.numel(), _stream()),
-                      'fcd_conv2d_bwd_weight_bias_cat')
-        elif want_db:
-            db = _channel_sum(dy, yrelu, d.N, d.K, d.P * d.Q)
+                                                   _pair_cat_ptrs(df, du, half), chans, 3, _p(ws), ws.numel(), _stream()),
+                  'fcd_conv2d_bwd_data_wino_cat')
+        dw, db = _weight_bias_grads(d, dy, yrelu, weight, ctx.bias_param, ctx.needs_input_grad[2],
+                                    has_bias and ctx.needs_input_grad[3], vk=vk, cat=(f2n, up, chans, half))
         return df, du, dw, db, None, None, None
 
 
@@ -486,15 +481,13 @@ def conv3x3_pair_cat_ok(f2n, up, weight):
         return False
     if not (f2n.is_cuda and up.is_cuda and f2n.is_contiguous() and up.is_contiguous()):
         return False
-    d = _desc((n, 2 * c + cu, H, W), weight.shape, 1, 1)
-    return bool(lib.fcd_conv_wino_cat_ok(ctypes.byref(d)))
+    return bool(lib.fcd_conv_wino_cat_ok(ctypes.byref(_pair_cat_geom(f2n.shape, up.shape, weight.shape)[0])))
 
 
 def conv3x3_pair_cat(f2n, up, weight, bias=None, relu=False, bn_groups=0):
     """conv3x3(cat([f2n[:n], f2n[n:], up], dim=1)) (+bias, + fused ReLU) without building the concatenation; check with
     :func:`conv3x3_pair_cat_ok` first.  ``bn_groups``: see :func:`conv2d`."""
-    n, cu, H, W = up.shape
-    d = _desc((n, 2 * f2n.shape[1] + cu, H, W), weight.shape, 1, 1)
+    d = _pair_cat_geom(f2n.shape, up.shape, weight.shape)[0]
     part = _bn_part(d, bn_groups, relu, up.device)
     return _tag_bn(_ConvPairCat.apply(f2n, up, weight, bias, bool(relu), part, int(bn_groups)), d, part, bn_groups)
 
@@ -750,6 +743,40 @@ def sync_bn_active():
     return bool(_sync_world())
 
 
+def _momentum(bn):
+    return bn.momentum if bn.momentum is not None else 0.1
+
+
+def _bn_grad_out(want, gamma, beta, device):
+    """``(dgamma, dbeta)`` buffers of an affine BatchNorm (the kernels write both or neither), ``(None, None)`` when not wanted."""
+    if not want:
+        return None, None
+    return _grad_out(gamma, gamma.shape, device), _grad_out(beta, beta.shape, device)
+
+
+def _bn_train_fusable(z, bn):
+    """What every fused consumer of a BatchNorm input asks first: a float32 CUDA 4-D tensor, a train-mode affine BatchNorm, no
+    SyncBN exchange."""
+    return (torch.is_tensor(z) and z.is_cuda and z.dim() == 4 and z.dtype == torch.float32
+            and (bn.training or bn.running_mean is None) and bn.weight is not None and bn.bias is not None and not _sync_world())
+
+
+def _bn_train_stats(z, gamma, beta, running_mean, running_var, momentum, eps, groups, parts):
+    """Train-mode statistics of ``z`` for a fused consumer: one (4, groups * C) block {save_mean, save_invstd, scale, shift}, from
+    the producing convolution's partial sums when ``parts`` (:func:`_bn_parts`) has them, and the running-statistics update."""
+    N, C, H, W = z.shape
+    st = torch.empty(4, groups * C, dtype=torch.float32, device=z.device)
+    ws = _ws(lib.fcd_bn_act_ws_bytes(C, groups), z.device)
+    buf, split = parts if parts is not None else (None, 0)
+    check(lib.fcd_bn_train_stats(_p(z), N, C, H * W, groups, _p(buf), split, _p(gamma), _p(beta), _p(running_mean), _p(running_var),
+                                 float(momentum), float(eps), _p(st[0]), _p(st[1]), _p(st[2]), _p(st[3]), _p(ws), ws.numel(),
+                                 _stream()), 'fcd_bn_train_stats')
+    if running_mean is not None:
+        # (the kernel moved the running statistics through raw pointers: see _BnAct.forward)
+        torch._C._increment_version([running_mean, running_var])
+    return st
+
+
 class _BnAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, slope, running_mean, running_var, training, momentum, eps, groups, act,
@@ -764,9 +791,7 @@ class _BnAct(torch.autograd.Function):
             save_invstd = torch.empty(groups * C, dtype=torch.float32, device=x.device)
         ws = _ws(lib.fcd_bn_act_ws_bytes(C, groups), x.device)
         world = _sync_world() if (has_bn and training) else 0
-        parts = getattr(x, '_fcd_bn', None) if (has_bn and training and not world) else None
-        if parts is not None and (parts[3] != x.data_ptr() or parts[4] != x._version):
-            parts = None
+        parts = _bn_parts(x, groups) if (has_bn and training and not world) else None
         if order is not None:
             # running statistics replayed in `order` (a group normalised once, counted as often as the reference calls the layer on it)
             if not (has_bn and training) or world:
@@ -776,7 +801,7 @@ class _BnAct(torch.autograd.Function):
                                             _p(running_mean), _p(running_var), float(momentum), float(eps), _p(save_mean),
                                             _p(save_invstd), act, _p(slope), float(slope_imm), _p(ws), ws.numel(), _stream()),
                   'fcd_bn_act_fwd_replay')
-        elif parts is not None and parts[2] == groups and parts[1] > 0:
+        elif parts is not None:
             # the producing convolution's output transform already summed y and y^2 per workgroup (conv2d(bn_groups=...))
             check(lib.fcd_bn_act_fwd_parts(_p(x), _p(y), N, C, H * W, groups, _p(parts[0]), parts[1], _p(gamma), _p(beta),
                                            _p(running_mean), _p(running_var), float(momentum), float(eps), _p(save_mean),
@@ -838,9 +863,7 @@ class _BnAct(torch.autograd.Function):
                                            _p(beta), _p(save_mean), _p(save_invstd), act, _p(slope), slope_imm, _p(ws),
                                            ws.numel(), _stream()), 'fcd_bn_bwd_from_sums')
             return dx, dgamma, dbeta, dslope, None, None, None, None, None, None, None, None, None
-        if has_bn and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
-            dgamma = _grad_out(gamma, (C,), x.device)
-            dbeta = _grad_out(beta, (C,), x.device)
+        dgamma, dbeta = _bn_grad_out(has_bn and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]), gamma, beta, x.device)
         if slope is not None and ctx.needs_input_grad[3]:
             dslope = _grad_out(slope, tuple(slope.shape), x.device)
         check(lib.fcd_bn_act_bwd(_p(dz), _p(x), _p(dx), N, C, H * W, groups, int(has_bn), _p(gamma), _p(beta),
@@ -864,66 +887,47 @@ class _BnReluConv2d(torch.autograd.Function):
     def forward(ctx, z, gamma, beta, running_mean, running_var, momentum, eps, groups, weight, bias, parts, bn_part, bn_groups):
         z = _dev(z, 'bn input')
         _dev(weight, 'conv weight')
-        N, C, H, W = z.shape
         d = _desc(z.shape, weight.shape, 1, 1)
         dev = z.device
-        save_mean = torch.empty(groups * C, dtype=torch.float32, device=dev)
-        save_invstd = torch.empty(groups * C, dtype=torch.float32, device=dev)
-        sc = torch.empty(2, groups * C, dtype=torch.float32, device=dev)
-        ws = _ws(lib.fcd_bn_act_ws_bytes(C, groups), dev)
-        check(lib.fcd_bn_train_stats(_p(z), N, C, H * W, groups, _p(parts[0]) if parts is not None else None,
-                                     parts[1] if parts is not None else 0, _p(gamma), _p(beta), _p(running_mean), _p(running_var),
-                                     float(momentum), float(eps), _p(save_mean), _p(save_invstd), _p(sc[0]), _p(sc[1]), _p(ws),
-                                     ws.numel(), _stream()), 'fcd_bn_train_stats')
-        if running_mean is not None:
-            torch._C._increment_version([running_mean, running_var])
+        st = _bn_train_stats(z, gamma, beta, running_mean, running_var, momentum, eps, groups, parts)
         y = torch.empty((d.N, d.K, d.P, d.Q), dtype=torch.float32, device=dev)
         b = _dev(bias, 'conv bias') if bias is not None else None
         vk = _keepv(d, ctx.needs_input_grad[8], dev)
         ex = _lib.WinoFwdExtras(vk.data_ptr() if vk is not None else None, bn_part.data_ptr() if bn_part is not None else None,
-                                int(bn_groups), int(groups), sc[0].data_ptr(), sc[1].data_ptr())
+                                int(bn_groups), int(groups), st[2].data_ptr(), st[3].data_ptr())
         wsc = _ws(lib.fcd_conv_wino_ws_bytes(ctypes.byref(d), 0), dev)
         check(lib.fcd_conv2d_fwd_wino_x(ctypes.byref(d), _p(z), _p(wino_weight(weight, 0, 4)), _p(b), _p(y), 0, None, None, _p(wsc),
                                         wsc.numel(), ctypes.byref(ex), _stream()), 'fcd_conv2d_fwd_wino_x')
         if ctx.needs_input_grad[8] and vk is None:
             raise _lib.FcdError('bn_relu_conv3x3: the layer keeps no transformed input for its weight gradient (check bn_relu_conv3x3_ok)')
-        ctx.save_for_backward(z, gamma, beta, save_mean, save_invstd, weight, vk)
+        ctx.save_for_backward(z, gamma, beta, st, weight, vk)
         ctx.cfg = (float(eps), int(groups), bias is not None)
         ctx.bias_param = bias
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        z, gamma, beta, save_mean, save_invstd, weight, vk = ctx.saved_tensors
+        z, gamma, beta, st, weight, vk = ctx.saved_tensors
         eps, groups, has_bias = ctx.cfg
         dy = _dev(dy, 'conv grad')
         N, C, H, W = z.shape
         d = _desc(z.shape, weight.shape, 1, 1)
         dev = dy.device
-        dz = dgamma = dbeta = dw = db = None
+        dz = dgamma = dbeta = None
         want_bn = ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         if want_bn:
             da = torch.empty(z.shape, dtype=torch.float32, device=dev)      # gradient of the activation that was never stored
             _bwd_data_conv(d, dy, weight, da)
             dz = torch.empty_like(z)
-            if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-                dgamma = _grad_out(gamma, (C,), dev)
-                dbeta = _grad_out(beta, (C,), dev)
+            dgamma, dbeta = _bn_grad_out(ctx.needs_input_grad[1] or ctx.needs_input_grad[2], gamma, beta, dev)
             ws = _ws(lib.fcd_bn_act_ws_bytes(C, groups), dev)
             check(lib.fcd_bn_act_bwd(_p(da), _p(z), _p(dz), N, C, H * W, groups, 1, _p(gamma), _p(beta), None, None, eps, 1,
-                                     _p(save_mean), _p(save_invstd), ACT_RELU, None, 0.0, _p(dgamma), _p(dbeta), None, _p(ws),
+                                     _p(st[0]), _p(st[1]), ACT_RELU, None, 0.0, _p(dgamma), _p(dbeta), None, _p(ws),
                                      ws.numel(), _stream()), 'fcd_bn_act_bwd')
             del da
-        want_db = has_bias and ctx.needs_input_grad[9]
-        if ctx.needs_input_grad[8]:
-            dw = _grad_out(weight, weight.shape, dev)
-            if want_db:
-                db = _grad_out(ctx.bias_param, (d.K,), dev)
-            ws = _ws(lib.fcd_conv2d_bwd_weight_ws_bytes(ctypes.byref(d)), dev)
-            check(lib.fcd_conv2d_bwd_weight_bias_v(ctypes.byref(d), _p(vk), _p(dy), None, _p(dw), _p(db), _p(ws), ws.numel(),
-                                                   _stream()), 'fcd_conv2d_bwd_weight_bias_v')
-        elif want_db:
-            db = _channel_sum(dy, None, d.N, d.K, d.P * d.Q)
+        # (the forward pass kept V or refused: with a weight gradient vk is there)
+        dw, db = _weight_bias_grads(d, dy, None, weight, ctx.bias_param, ctx.needs_input_grad[8],
+                                    has_bias and ctx.needs_input_grad[9], vk=vk)
         return dz, dgamma, dbeta, None, None, None, None, None, dw, db, None, None, None
 
 
@@ -931,9 +935,7 @@ def bn_relu_conv3x3_ok(z, bn, weight, groups=1):
     """True when ``conv2d(bn_act(z, bn, ACT_RELU, groups=groups), weight, bias, 1, 1)`` can run as :func:`bn_relu_conv3x3`:
     train-mode affine BatchNorm with per-replica statistics in front of a 3x3 / stride-1 / pad-1 layer whose forward runs as
     F(4x4) through the rolling input transform and which keeps its transformed input for the weight gradient."""
-    if not (torch.is_tensor(z) and z.is_cuda and z.dim() == 4 and z.dtype == torch.float32):
-        return False
-    if not (bn.training or bn.running_mean is None) or bn.weight is None or bn.bias is None or _sync_world():
+    if not _bn_train_fusable(z, bn):
         return False
     if tuple(weight.shape[2:]) != (3, 3) or weight.shape[1] != z.shape[1] or z.shape[0] % groups:
         return False
@@ -946,14 +948,10 @@ def bn_relu_conv3x3_ok(z, bn, weight, groups=1):
 def bn_relu_conv3x3(z, bn, weight, bias=None, groups=1, bn_groups=0):
     """``conv2d(bn_act(z, bn, ACT_RELU, groups=groups), weight, bias, 1, 1, bn_groups=bn_groups)`` without the activation tensor
     (:class:`_BnReluConv2d`; check :func:`bn_relu_conv3x3_ok` first)."""
-    parts = getattr(z, '_fcd_bn', None)
-    if parts is not None and (parts[3] != z.data_ptr() or parts[4] != z._version or parts[2] != groups or parts[1] <= 0):
-        parts = None
     d = _desc(z.shape, weight.shape, 1, 1)
     part = _bn_part(d, bn_groups, False, z.device)
-    y = _BnReluConv2d.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                            bn.momentum if bn.momentum is not None else 0.1, bn.eps, int(groups), weight, bias,
-                            (parts[0], parts[1]) if parts is not None else None, part, int(bn_groups) if part is not None else 0)
+    y = _BnReluConv2d.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, _momentum(bn), bn.eps, int(groups), weight, bias,
+                            _bn_parts(z, groups), part, int(bn_groups) if part is not None else 0)
     _count_batches(bn, groups)
     return _tag_bn(y, d, part, bn_groups)
 
@@ -1018,9 +1016,8 @@ def bn_act(x, bn=None, act=ACT_NONE, slope=None, slope_imm=0.0, groups=1, order=
     if order is not None and not (training and bn.running_mean is not None):
         order = None
     calls = len(order) if order is not None else groups
-    y = _BnAct.apply(x, bn.weight, bn.bias, slope, bn.running_mean, bn.running_var, training,
-                     bn.momentum if bn.momentum is not None else 0.1, bn.eps, groups, act, slope_imm,
-                     tuple(order) if order is not None else None)
+    y = _BnAct.apply(x, bn.weight, bn.bias, slope, bn.running_mean, bn.running_var, training, _momentum(bn), bn.eps, groups, act,
+                     slope_imm, tuple(order) if order is not None else None)
     if training:
         _count_batches(bn, calls)
     return y
@@ -1037,8 +1034,8 @@ class _Conv1x1Head(torch.autograd.Function):
         N, C, H, W = x.shape
         w = weight.detach().reshape(-1).contiguous()
         y = torch.empty((N, 1, H, W), dtype=torch.float32, device=x.device)
-        check(lib.fcd_conv1x1_head_fwd(_p(x), _p(w), _p(bias) if bias is not None else None, _p(y), N, C, H * W,
-                                       1 if sigmoid else 0, _stream()), 'fcd_conv1x1_head_fwd')
+        check(lib.fcd_conv1x1_head_fwd(_p(x), _p(w), _p(bias), _p(y), N, C, H * W, 1 if sigmoid else 0, _stream()),
+              'fcd_conv1x1_head_fwd')
         ctx.sigmoid = bool(sigmoid)
         ctx.has_bias = bias is not None
         ctx.wshape = tuple(weight.shape)
@@ -1064,10 +1061,8 @@ class _Conv1x1Head(torch.autograd.Function):
             nbytes = int(lib.fcd_conv1x1_head_bwd_ws_bytes(N, C))
             ws = torch.empty(nbytes, dtype=torch.uint8, device=dy.device)
         if want_dx or want_dw or want_db:
-            check(lib.fcd_conv1x1_head_bwd(_p(x) if x is not None else None, _p(w), _p(dy), _p(y) if y is not None else None,
-                                           _p(dx) if dx is not None else None, _p(dw) if dw is not None else None,
-                                           _p(db) if db is not None else None, N, C, H * W,
-                                           _p(ws) if ws is not None else None, nbytes, _stream()), 'fcd_conv1x1_head_bwd')
+            check(lib.fcd_conv1x1_head_bwd(_p(x), _p(w), _p(dy), _p(y), _p(dx), _p(dw), _p(db), N, C, H * W, _p(ws), nbytes, _stream()),
+                  'fcd_conv1x1_head_bwd')
         return dx, (dw.view(ctx.wshape) if dw is not None else None), db, None
 
 
@@ -1080,19 +1075,11 @@ class _BnReluHead(torch.autograd.Function):
     def forward(ctx, z, gamma, beta, running_mean, running_var, momentum, eps, groups, weight, bias, sigmoid, parts):
         z = _dev(z, 'bn input')
         N, C, H, W = z.shape
-        dev = z.device
-        st = torch.empty(4, groups * C, dtype=torch.float32, device=dev)      # save_mean, save_invstd, scale, shift
-        ws = _ws(lib.fcd_bn_act_ws_bytes(C, groups), dev)
-        check(lib.fcd_bn_train_stats(_p(z), N, C, H * W, groups, _p(parts[0]) if parts is not None else None,
-                                     parts[1] if parts is not None else 0, _p(gamma), _p(beta), _p(running_mean), _p(running_var),
-                                     float(momentum), float(eps), _p(st[0]), _p(st[1]), _p(st[2]), _p(st[3]), _p(ws), ws.numel(),
-                                     _stream()), 'fcd_bn_train_stats')
-        if running_mean is not None:
-            torch._C._increment_version([running_mean, running_var])
+        st = _bn_train_stats(z, gamma, beta, running_mean, running_var, momentum, eps, groups, parts)
         w = weight.detach().reshape(-1).contiguous()
-        y = torch.empty((N, 1, H, W), dtype=torch.float32, device=dev)
-        check(lib.fcd_conv1x1_head_bn_fwd(_p(z), _p(st[2]), _p(st[3]), groups, _p(w), _p(bias) if bias is not None else None, _p(y),
-                                          N, C, H * W, 1 if sigmoid else 0, _stream()), 'fcd_conv1x1_head_bn_fwd')
+        y = torch.empty((N, 1, H, W), dtype=torch.float32, device=z.device)
+        check(lib.fcd_conv1x1_head_bn_fwd(_p(z), _p(st[2]), _p(st[3]), groups, _p(w), _p(bias), _p(y), N, C, H * W,
+                                          1 if sigmoid else 0, _stream()), 'fcd_conv1x1_head_bn_fwd')
         ctx.save_for_backward(z, w, y if sigmoid else None, st, gamma, beta)
         ctx.cfg = (int(groups), bias is not None, tuple(weight.shape))
         ctx.bias_param = bias
@@ -1109,13 +1096,10 @@ class _BnReluHead(torch.autograd.Function):
         dz = torch.empty_like(z)
         dw = _grad_out(ctx.weight_param, wshape, dev) if ctx.needs_input_grad[8] else None
         db = _grad_out(ctx.bias_param, (1,), dev) if (has_bias and ctx.needs_input_grad[9]) else None
-        dgamma = dbeta = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            dgamma = _grad_out(gamma, (C,), dev)
-            dbeta = _grad_out(beta, (C,), dev)
+        dgamma, dbeta = _bn_grad_out(ctx.needs_input_grad[1] or ctx.needs_input_grad[2], gamma, beta, dev)
         nb = int(lib.fcd_conv1x1_head_bn_bwd_ws_bytes(N, C, groups))
         ws = _ws(nb, dev)
-        check(lib.fcd_conv1x1_head_bn_bwd(_p(z), _p(w), _p(dy), _p(y) if y is not None else None, _p(st[2]), _p(st[3]), _p(st[0]),
+        check(lib.fcd_conv1x1_head_bn_bwd(_p(z), _p(w), _p(dy), _p(y), _p(st[2]), _p(st[3]), _p(st[0]),
                                           _p(st[1]), groups, _p(dz), _p(dw), _p(db), _p(dgamma), _p(dbeta), N, C, H * W, _p(ws),
                                           ws.numel(), _stream()), 'fcd_conv1x1_head_bn_bwd')
         return dz, dgamma, dbeta, None, None, None, None, None, dw, db, None, None
@@ -1132,17 +1116,9 @@ class _BnReluPoolSkip(torch.autograd.Function):
     def forward(ctx, z, gamma, beta, running_mean, running_var, momentum, eps, groups, parts):
         z = _dev(z, 'bn input')
         N, C, H, W = z.shape
-        dev = z.device
-        st = torch.empty(4, groups * C, dtype=torch.float32, device=dev)      # save_mean, save_invstd, scale, shift
-        ws = _ws(lib.fcd_bn_act_ws_bytes(C, groups), dev)
-        check(lib.fcd_bn_train_stats(_p(z), N, C, H * W, groups, _p(parts[0]) if parts is not None else None,
-                                     parts[1] if parts is not None else 0, _p(gamma), _p(beta), _p(running_mean), _p(running_var),
-                                     float(momentum), float(eps), _p(st[0]), _p(st[1]), _p(st[2]), _p(st[3]), _p(ws), ws.numel(),
-                                     _stream()), 'fcd_bn_train_stats')
-        if running_mean is not None:
-            torch._C._increment_version([running_mean, running_var])
+        st = _bn_train_stats(z, gamma, beta, running_mean, running_var, momentum, eps, groups, parts)
         a = torch.empty_like(z)
-        p = torch.empty((N, C, H // 2, W // 2), dtype=torch.float32, device=dev)
+        p = torch.empty((N, C, H // 2, W // 2), dtype=torch.float32, device=z.device)
         check(lib.fcd_bn_relu_pool_fwd(_p(z), _p(a), _p(p), N, C, H, W, groups, _p(st[2]), _p(st[3]), _stream()), 'fcd_bn_relu_pool_fwd')
         ctx.save_for_backward(z, gamma, beta, st)
         ctx.groups = int(groups)
@@ -1160,10 +1136,7 @@ class _BnReluPoolSkip(torch.autograd.Function):
         da = _dev(da, 'skip grad') if da is not None else torch.zeros_like(z)
         dp = _dev(dp, 'maxpool grad') if dp is not None else torch.zeros((N, C, H // 2, W // 2), dtype=torch.float32, device=dev)
         dz = torch.empty_like(z)
-        dgamma = dbeta = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            dgamma = _grad_out(gamma, (C,), dev)
-            dbeta = _grad_out(beta, (C,), dev)
+        dgamma, dbeta = _bn_grad_out(ctx.needs_input_grad[1] or ctx.needs_input_grad[2], gamma, beta, dev)
         ws = _ws(lib.fcd_bn_act_ws_bytes(C, groups), dev)
         check(lib.fcd_bn_relu_pool_bwd(_p(z), _p(da), _p(dp), _p(dz), N, C, H, W, groups, _p(gamma), _p(beta), _p(st[0]), _p(st[1]),
                                        _p(dgamma), _p(dbeta), _p(ws), ws.numel(), _stream()), 'fcd_bn_relu_pool_bwd')
@@ -1172,11 +1145,7 @@ class _BnReluPoolSkip(torch.autograd.Function):
 
 def bn_relu_pool_skip_ok(z, bn, groups=1):
     """True when ``a = bn_act(z, bn, ACT_RELU, groups); (a, maxpool2(a))`` can run as :func:`bn_relu_pool_skip`."""
-    if not (torch.is_tensor(z) and z.is_cuda and z.dim() == 4 and z.dtype == torch.float32):
-        return False
-    if not switch('BN_FUSE') or _sync_world():
-        return False
-    if not (bn.training or bn.running_mean is None) or bn.weight is None or bn.bias is None:
+    if not _bn_train_fusable(z, bn) or not switch('BN_FUSE'):
         return False
     N, C, H, W = z.shape
     return bool(lib.fcd_bn_relu_pool_plan(N, C, H, W, int(groups)))
@@ -1184,22 +1153,15 @@ def bn_relu_pool_skip_ok(z, bn, groups=1):
 
 def bn_relu_pool_skip(z, bn, groups=1):
     """``a = relu(bn(z))`` and ``maxpool2(a)`` from one node (:class:`_BnReluPoolSkip`; check :func:`bn_relu_pool_skip_ok` first)."""
-    parts = getattr(z, '_fcd_bn', None)
-    if parts is not None and (parts[3] != z.data_ptr() or parts[4] != z._version or parts[2] != groups or parts[1] <= 0):
-        parts = None
-    out = _BnReluPoolSkip.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum if bn.momentum is not None else 0.1,
-                                bn.eps, int(groups), (parts[0], parts[1]) if parts is not None else None)
+    out = _BnReluPoolSkip.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, _momentum(bn), bn.eps, int(groups),
+                                _bn_parts(z, groups))
     _count_batches(bn, groups)
     return out
 
 
 def bn_relu_head_ok(z, bn, weight, groups=1):
     """True when ``conv1x1_head(bn_act(z, bn, ACT_RELU, groups=groups), weight, bias)`` can run as :func:`bn_relu_head`."""
-    if not (torch.is_tensor(z) and z.is_cuda and z.dim() == 4 and z.dtype == torch.float32):
-        return False
-    if not switch('BN_FUSE') or _sync_world():
-        return False
-    if not (bn.training or bn.running_mean is None) or bn.weight is None or bn.bias is None or z.shape[0] % groups:
+    if not _bn_train_fusable(z, bn) or not switch('BN_FUSE') or z.shape[0] % groups:
         return False
     return conv1x1_head_supported(z, weight) and weight.shape[1] == z.shape[1]
 
@@ -1207,11 +1169,8 @@ def bn_relu_head_ok(z, bn, weight, groups=1):
 def bn_relu_head(z, bn, weight, bias, sigmoid=True, groups=1):
     """``conv1x1_head(bn_act(z, bn, ACT_RELU, groups=groups), weight, bias, sigmoid)`` without the activation tensor
     (:class:`_BnReluHead`; check :func:`bn_relu_head_ok` first)."""
-    parts = getattr(z, '_fcd_bn', None)
-    if parts is not None and (parts[3] != z.data_ptr() or parts[4] != z._version or parts[2] != groups or parts[1] <= 0):
-        parts = None
-    out = _BnReluHead.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum if bn.momentum is not None else 0.1,
-                            bn.eps, int(groups), weight, bias, bool(sigmoid), (parts[0], parts[1]) if parts is not None else None)
+    out = _BnReluHead.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, _momentum(bn), bn.eps, int(groups), weight, bias,
+                            bool(sigmoid), _bn_parts(z, groups))
     _count_batches(bn, groups)
     return out
 
@@ -1400,8 +1359,8 @@ class _MaskedStack(torch.autograd.Function):
         ds = [torch.empty_like(ts[i]) if need[1 + i] else None for i in range(k)]
         if dcm is not None or any(d is not None for d in ds):
             ptr = [_p(t) for t in ts] + [None] * (4 - k)
-            dp = [(_p(d) if d is not None else None) for d in ds] + [None] * (4 - k)
-            check(lib.fcd_masked_stack_bwd(_p(dz), ptr[0], ptr[1], ptr[2], ptr[3], k, _p(cm), _p(dcm) if dcm is not None else None,
+            dp = [_p(d) for d in ds] + [None] * (4 - k)
+            check(lib.fcd_masked_stack_bwd(_p(dz), ptr[0], ptr[1], ptr[2], ptr[3], k, _p(cm), _p(dcm),
                                            dp[0], dp[1], dp[2], dp[3], N, C, H * W, _stream()), 'fcd_masked_stack_bwd')
         return (dcm,) + tuple(ds)
 

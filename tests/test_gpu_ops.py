@@ -668,6 +668,57 @@ def test_bn_relu_applied_by_the_next_convolutions_loader(case, tagged):
         assert torch.equal(a, r), (what, (a.double() - r.double()).abs().max().item())
 
 
+@pytest.mark.parametrize('G', [1, 2])
+def test_every_bn_consumer_uses_a_fresh_partial_sum_tag_and_ignores_a_stale_one(G):
+    """The output of ``conv2d(bn_groups=G)`` carries the BatchNorm partial sums of its F(4x4) output transform; all four consumers
+    (``bn_act``, ``bn_relu_conv3x3``, ``bn_relu_pool_skip``, ``bn_relu_head``) read them through one rule.  (a) Fresh tag: outputs and
+    running statistics against the same consumer fed an untagged clone -- same fp64 sums in another order, 2e-6 as in
+    test_bn_statistics_from_the_output_transform.  (b) After an in-place edit of z the tag describes other values (the mean is off by
+    a factor of two): every consumer must be BIT-identical to the same consumer fed an untagged clone of the edited tensor.
+    Shape: C = 64 -> K = 128 takes the F(4x4) plan with 512 tiles, a multiple of 256 per group for both G, so the tag is there."""
+    ops = _ops()
+    N, C, H, W, K = 2, 64, 64, 64, 128
+    x = rnd(N, C, H, W, seed=131).cuda()
+    w0 = rnd(K, C, 3, 3, seed=132, scale=(2.0 / (C * 9)) ** 0.5).cuda()
+    w1 = rnd(K, K, 3, 3, seed=133, scale=(2.0 / (K * 9)) ** 0.5).cuda()
+    b1 = rnd(K, seed=134, scale=0.1).cuda()
+    wh = rnd(1, K, 1, 1, seed=135, scale=K ** -0.5).cuda()
+    bh = rnd(1, seed=136, scale=0.1).cuda()
+    consumers = {
+        'bn_act': (lambda z, bn: True, lambda z, bn: (ops.bn_act(z, bn, ops.ACT_RELU, groups=G),)),
+        'bn_relu_conv3x3': (lambda z, bn: ops.bn_relu_conv3x3_ok(z, bn, w1, G),
+                            lambda z, bn: (ops.bn_relu_conv3x3(z, bn, w1, b1, groups=G),)),
+        'bn_relu_pool_skip': (lambda z, bn: ops.bn_relu_pool_skip_ok(z, bn, G), lambda z, bn: ops.bn_relu_pool_skip(z, bn, groups=G)),
+        'bn_relu_head': (lambda z, bn: ops.bn_relu_head_ok(z, bn, wh, G), lambda z, bn: (ops.bn_relu_head(z, bn, wh, bh, groups=G),)),
+    }
+
+    def run(z):
+        out = {}
+        for name, (ok, fn) in consumers.items():
+            bn = torch.nn.BatchNorm2d(K).cuda().train()
+            bn.weight.copy_(rnd(K, seed=137).cuda() * 0.2 + 1.0)
+            bn.bias.copy_(rnd(K, seed=138).cuda() * 0.1)
+            assert ok(z, bn), name
+            out[name] = [t.cpu() for t in fn(z, bn)] + [bn.running_mean.cpu(), bn.running_var.cpu()]
+            assert int(bn.num_batches_tracked) == G
+        return out
+
+    with torch.no_grad():
+        z = ops.conv2d(x, w0, None, 1, 1, bn_groups=G)
+        assert getattr(z, '_fcd_bn', None) is not None and getattr(z.clone(), '_fcd_bn', None) is None
+        fresh, plain = run(z), run(z.clone())
+        z.mul_(2.0)
+        assert getattr(z, '_fcd_bn', None) is not None          # still attached, now describing other values
+        stale, edited = run(z), run(z.clone())
+    for name in consumers:
+        assert len(fresh[name]) == len(plain[name]) == len(stale[name]) == len(edited[name]) >= 3
+        for i, (a, r) in enumerate(zip(fresh[name], plain[name])):
+            err = (a.double() - r.double()).abs().max().item() / max(r.abs().max().item(), 1e-12)
+            assert err < 2e-6, (name, i, err)
+        for i, (a, r) in enumerate(zip(stale[name], edited[name])):
+            assert torch.equal(a, r), (name, i, (a.double() - r.double()).abs().max().item())
+
+
 @pytest.mark.parametrize('shape', [(2, 3, 8, 8), (1, 5, 11, 13), (2, 4, 27, 55), (3, 16, 64, 64), (1, 2, 2, 2)], ids=lambda c: 'x'.join(map(str, c)))
 @pytest.mark.parametrize('use', ['both', 'skip_only', 'pool_only'])
 def test_maxpool_with_a_skip_consumer_sums_both_gradients_in_one_pass(shape, use):
