@@ -170,6 +170,11 @@ _SIGS = {
     'fcd_ssim_ws_bytes': (c_size_t, [c_int, c_int, c_int]),
     'fcd_ssim_level_fwd': (c_int, [P, P, P, c_int, P, c_int, c_int, c_int, c_float, c_float, P, c_size_t, P]),
     'fcd_ssim_level_bwd': (c_int, [P, P, P, c_int, P, P, P, P, c_int, c_int, c_int, c_float, c_float, P, c_size_t, P]),
+    'fcd_ssim3d_ws_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'fcd_ssim3d_level_fwd': (c_int, [P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_float, c_float, P, c_size_t, P]),
+    'fcd_ssim3d_level_bwd': (c_int, [P, P, P, c_int, P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, P, c_size_t, P]),
+    'fcd_avgpool3d2_pad_fwd': (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
+    'fcd_avgpool3d2_pad_bwd': (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     'fcd_adam_step': (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, c_int, c_float, P]),
     'fcd_rmsprop_step': (c_int, [P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, P]),
     'fcd_adam_step_h': (c_int, [P, P, P, P, c_int64, P, c_float, c_float, c_float, c_float, c_float, P]),

@@ -1296,7 +1296,46 @@ class _AvgPool2Pad(torch.autograd.Function):
         return dx
 
 
+def _pool_pad_extent(s):
+    return (s + 2 * (s % 2) - 2) // 2 + 1
+
+
+class _AvgPool3d2Pad(torch.autograd.Function):
+    """F.avg_pool3d(kernel 2, padding = size % 2 per dimension) of an (N, C, T, H, W) tensor (reference ssim.py:183-184,213-216)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = _dev(x, 'avgpool input')
+        N, C, T, H, W = x.shape
+        y = torch.empty((N, C, _pool_pad_extent(T), _pool_pad_extent(H), _pool_pad_extent(W)), dtype=torch.float32,
+                        device=x.device)
+        check(lib.fcd_avgpool3d2_pad_fwd(_p(x), _p(y), N * C, T, H, W, _stream()), 'fcd_avgpool3d2_pad_fwd')
+        ctx.shape = (N, C, T, H, W)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        N, C, T, H, W = ctx.shape
+        dy = _dev(dy, 'avgpool grad')
+        dx = torch.empty((N, C, T, H, W), dtype=torch.float32, device=dy.device)
+        check(lib.fcd_avgpool3d2_pad_bwd(_p(dy), _p(dx), N * C, T, H, W, _stream()), 'fcd_avgpool3d2_pad_bwd')
+        return dx
+
+
+def check_pool3d_extents(shape):
+    """ATen refuses to pool a dimension of extent 1 with a window of 2 (the reference's ``avg_pool3d`` raises RuntimeError);
+    so does this, before anything is launched."""
+    for name, s in zip('THW', shape[2:]):
+        if s < 2:
+            raise RuntimeError('avg_pool3d(kernel 2): input image (T: %d H: %d W: %d) smaller than kernel size (%s: %d)'
+                               % (tuple(shape[2:]) + (name, s)))
+
+
 def avgpool2_pad(x):
+    """The padded 2x average pool between MS-SSIM levels: (N, C, H, W) -> 2x2, (N, C, T, H, W) -> 2x2x2."""
+    if x.dim() == 5:
+        check_pool3d_extents(x.shape)
+        return _AvgPool3d2Pad.apply(x)
     return _AvgPool2Pad.apply(x)
 
 
@@ -1508,10 +1547,42 @@ class _SsimLevel(torch.autograd.Function):
         return dX, dY, None, None, None
 
 
+class _SsimLevel3d(torch.autograd.Function):
+    """The level on (N, C, T, H, W) inputs (csrc/ssim3d.hip)."""
+
+    @staticmethod
+    def forward(ctx, X, Y, win, C1, C2):
+        X = _dev(X, 'ssim X')
+        Y = _dev(Y, 'ssim Y')
+        win = _dev(win, 'ssim window')
+        N, C, T, H, W = X.shape
+        out = torch.empty(2 * N * C, dtype=torch.float32, device=X.device)
+        ws = _ws(16 * N * C * ((H + 15) // 16) * ((W + 31) // 32), X.device)   # fp64 {ssim, cs} per plane tile
+        check(lib.fcd_ssim3d_level_fwd(_p(X), _p(Y), _p(win), win.numel(), _p(out), N * C, T, H, W, C1, C2, _p(ws),
+                                       ws.numel(), _stream()), 'fcd_ssim3d_level_fwd')
+        ctx.save_for_backward(X, Y, win)
+        ctx.consts = (C1, C2)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        X, Y, win = ctx.saved_tensors
+        C1, C2 = ctx.consts
+        N, C, T, H, W = X.shape
+        NC = N * C
+        g = _dev(g, 'ssim grad')
+        gs, gc = g[:NC].contiguous(), g[NC:].contiguous()
+        dX, dY = torch.empty_like(X), torch.empty_like(Y)
+        ws = _ws(lib.fcd_ssim3d_ws_bytes(NC, T, H, W), X.device)
+        check(lib.fcd_ssim3d_level_bwd(_p(X), _p(Y), _p(win), win.numel(), _p(gs), _p(gc), _p(dX), _p(dY), NC, T, H, W,
+                                       C1, C2, _p(ws), ws.numel(), _stream()), 'fcd_ssim3d_level_bwd')
+        return dX, dY, None, None, None
+
+
 def ssim_level(X, Y, win, C1, C2):
-    """(ssim_mean[N,C], cs_mean[N,C]) -- ssim.py:55-92."""
+    """(ssim_mean[N,C], cs_mean[N,C]) -- ssim.py:55-92; (N, C, H, W) or (N, C, T, H, W) inputs."""
     N, C = X.shape[0], X.shape[1]
-    out = _SsimLevel.apply(X, Y, win, float(C1), float(C2))
+    out = (_SsimLevel3d if X.dim() == 5 else _SsimLevel).apply(X, Y, win, float(C1), float(C2))
     return out[:N * C].view(N, C), out[N * C:].view(N, C)
 
 

@@ -443,6 +443,28 @@ int fcd_ssim_level_bwd(const float* X, const float* Y, const float* win, int win
                        const float* g_ssim, const float* g_cs, float* dX, float* dY, int NC, int H,
                        int W, float C1, float C2, void* ws, size_t ws_bytes, void* stream);
 
+/* Volumetric SSIM level: the same function on (N,C,T,H,W) inputs (ssim.py:26-52 with F.conv3d, :55-92) -- the odd window
+ * `win` (<= 11 taps) applied VALID along T, H and W, each dimension shorter than the window left unsmoothed (ssim.py:44-50:
+ * single tap 1, output extent = input extent), ssim_map / cs_map averaged over OT*OH*OW per (n,c).
+ * out[2*NC] = {ssim_mean[NC], cs_mean[NC]}.  X, Y: NC*T*H*W floats.  An even window or one longer than 11 taps: -1.
+ * fcd_ssim3d_ws_bytes = max(forward: 16 * NC * ceil(H/16) * ceil(W/32)  (one fp64 {ssim, cs} pair per (n,c) and plane tile),
+ *                           backward: 16 * NC * T * H * W               (four fp32 adjoint maps, bounded by the input volume));
+ * 0 for a non-positive extent.  The forward call itself needs only its own term. */
+size_t fcd_ssim3d_ws_bytes(int NC, int T, int H, int W);
+int fcd_ssim3d_level_fwd(const float* X, const float* Y, const float* win, int win_size, float* out,
+                         int NC, int T, int H, int W, float C1, float C2, void* ws, size_t ws_bytes, void* stream);
+/* Backward: g_ssim[NC], g_cs[NC] are the upstream grads of the two means; writes dX, dY (NC*T*H*W each).
+ * ws: fcd_ssim3d_ws_bytes() (the adjoint maps dmu1, dmu2, dB2, de12, each [NC][OT][OH][OW]). */
+int fcd_ssim3d_level_bwd(const float* X, const float* Y, const float* win, int win_size, const float* g_ssim,
+                         const float* g_cs, float* dX, float* dY, int NC, int T, int H, int W, float C1, float C2,
+                         void* ws, size_t ws_bytes, void* stream);
+/* F.avg_pool3d(kernel 2, padding = size % 2 per dimension) between the levels of a volumetric MS-SSIM (ssim.py:183-184,
+ * :213-216): padding is counted, the divisor is always 8; output extent (S + 2p - 2)/2 + 1 per dimension.  x: NC*T*H*W floats
+ * (the INPUT extents in both directions).  bwd: dx = dy/8 gathered at ((t+pt)>>1, (h+ph)>>1, (w+pw)>>1), 0 where that index
+ * lies outside y.  T, H or W < 2: -1 (ATen refuses such an input too: "smaller than kernel size"). */
+int fcd_avgpool3d2_pad_fwd(const float* x, float* y, int NC, int T, int H, int W, void* stream);
+int fcd_avgpool3d2_pad_bwd(const float* dy, float* dx, int NC, int T, int H, int W, void* stream);
+
 /* ---- data gradient of 3x3 / stride-2 / pad-1 convolutions by sub-pixel decomposition: one stride-1 pseudo-convolution with
  * 2x2 taps over dy producing the four phases of dx (16 instead of 36 multiplies per input-pixel quad), rows scattered to
  * their sub-pixel positions by the epilogue.  fcd_conv_s2_dgrad_plan: 1 when the layer takes this form; filters are then
