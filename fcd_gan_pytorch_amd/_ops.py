@@ -1013,6 +1013,9 @@ def bn_act(x, bn=None, act=ACT_NONE, slope=None, slope_imm=0.0, groups=1, order=
     if bn is None:
         return _BnAct.apply(x, None, None, slope, None, None, False, 0.0, 0.0, groups, act, slope_imm)
     training = bn.training or bn.running_mean is None
+    if training and x.numel() // x.shape[1] == groups:
+        # one value per channel and group: the batch variance is 0 / 0 (torch.nn.functional.batch_norm raises the same)
+        raise ValueError('Expected more than 1 value per channel when training, got input size %s' % (tuple(x.shape),))
     if order is not None and not (training and bn.running_mean is not None):
         order = None
     calls = len(order) if order is not None else groups

@@ -107,9 +107,12 @@ __device__ __forceinline__ double block_sum_d(double v, double* smem /* >= 16 do
 
 // activation codes shared by host + device
 // act: 0 none, 1 ReLU, 2 LeakyReLU(slope scalar), 3 PReLU(slope from device pointer)
+// ReLU is written `v <= 0 ? 0 : v`, not `v > 0 ? v : 0`: a NaN fails both compares and must come out as NaN (ATen's relu), the
+// leaky / PReLU branch already passes it on through v * slope.
+__device__ __forceinline__ float relu_nan(float v) { return v <= 0.f ? 0.f : v; }
 __device__ __forceinline__ float act_apply(float v, int act, float slope) {
   if (act == FCD_ACT_NONE) return v;
-  if (act == FCD_ACT_RELU) return v > 0.f ? v : 0.f;
+  if (act == FCD_ACT_RELU) return relu_nan(v);
   return v > 0.f ? v : v * slope;
 }
 // derivative factor d act(v) / d v  (PyTorch convention: slope branch at v <= 0)

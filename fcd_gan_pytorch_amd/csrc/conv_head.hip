@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256) void head_fwd_bn_kernel(const float* __restric
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float yv = fmaf(v[e], s, t);
-      r[e] = yv > 0.f ? yv : 0.f;
+      r[e] = relu_nan(yv);
     }
     return r;
   };

@@ -430,7 +430,7 @@ __global__ __launch_bounds__(256) void wino_input_roll_kernel(WinoInArgs a, int 
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float y = fmaf(pre[k][e], asc[k], ash[k]);
-          t[e] = (in && y > 0.f) ? y : 0.f;
+          t[e] = in ? relu_nan(y) : 0.f;
         }
       } else {
         if (SRC == 1 && a.mbits) {
@@ -456,7 +456,7 @@ __global__ __launch_bounds__(256) void wino_input_roll_kernel(WinoInArgs a, int 
         const int ih = ty * MM - 1 + r, iw = iw0 + col;
         const bool in = q * 32 + c < a.C && ih >= 0 && ih < a.H && iw >= 0 && iw < a.W;
         const float y = fmaf(preh[k], hsc[k], hsh[k]);
-        tile[c * PL + r * CW + col] = (in && y > 0.f) ? y : 0.f;
+        tile[c * PL + r * CW + col] = in ? relu_nan(y) : 0.f;
       } else {
         tile[c * PL + r * CW + col] = ((SRC == 1 || SRC == 2) && !(mskh[k] > 0.f)) ? 0.f : preh[k];
       }

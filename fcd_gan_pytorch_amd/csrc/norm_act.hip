@@ -736,8 +736,8 @@ __global__ __launch_bounds__(256) void bn_relu_pool_fwd_kernel(const float* __re
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float y0 = fmaf(z0[e], sc, sh), y1 = fmaf(z1[e], sc, sh);
-      a0[e] = y0 > 0.f ? y0 : 0.f;
-      a1[e] = y1 > 0.f ? y1 : 0.f;
+      a0[e] = relu_nan(y0);
+      a1[e] = relu_nan(y1);
     }
     *(bnp_f4*)(ap + o) = a0;
     *(bnp_f4*)(ap + o + W) = a1;
@@ -764,8 +764,8 @@ __device__ __forceinline__ BnPoolPatch bn_pool_patch(const float* __restrict__ z
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const float y0 = fmaf(q.z0[e], sc, sh), y1 = fmaf(q.z1[e], sc, sh);
-    a0[e] = y0 > 0.f ? y0 : 0.f;
-    a1[e] = y1 > 0.f ? y1 : 0.f;
+    a0[e] = relu_nan(y0);
+    a1[e] = relu_nan(y1);
   }
   float t;
   const int g0 = pool_arg(a0[0], a0[1], a1[0], a1[1], &t), g1 = pool_arg(a0[2], a0[3], a1[2], a1[3], &t);
