@@ -162,6 +162,10 @@ _SIGS = {
     'fcd_masked_stack_fwd': (c_int, [P, P, P, P, c_int, P, P, c_int, c_int, c_int, P]),
     'fcd_masked_stack_bwd': (c_int, [P, P, P, P, P, c_int, P, P, P, P, P, P, c_int, c_int, c_int, P]),
     'fcd_normalize_tiles': (c_int, [P, P, P, P, P, c_int, c_int, c_int, P]),
+    'fcd_scene_cut': (c_int, [P, P, c_int, P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, P, P, P, P, P, P]),
+    'fcd_scene_stitch': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int,
+                                 P, c_int, c_int, P, P, P, P]),
+    'fcd_tile_confusion': (c_int, [P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, P, P]),
     'fcd_masked_recon_ws_bytes': (c_size_t, [c_int]),
     'fcd_masked_recon_fwd': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
     'fcd_masked_recon_bwd': (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),

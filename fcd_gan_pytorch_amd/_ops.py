@@ -1436,6 +1436,204 @@ def normalize_tiles(x, mean, std, valid=None, out=None):
     return out
 
 
+# ------------------------------------------------------- device-resident scene inference (csrc/scene.hip)
+SAMPLE_U8, SAMPLE_U16, SAMPLE_F32 = 0, 1, 2
+# torch dtype of a resident scene -> sample type of the C ABI (a uint16 scene may travel as int16 bits: ``sample_type=``)
+_SAMPLE_OF = {torch.uint8: SAMPLE_U8, torch.uint16: SAMPLE_U16, torch.float32: SAMPLE_F32}
+
+
+class TileTable:
+    """A validated tile table: ``rows`` = host int32 (n,12) array, row = ``TileGrid.slices(item)`` flattened (own x0,y0,w,h | read
+    rx,ry,rw,rh | canvas wx,wy,ww,wh), ``geom`` = the (W, H, pw, ph, padx, pady) it was validated against and, after
+    :meth:`to`, the device copy the kernels read.  Only :func:`scene_tile_table` makes one, so a kernel never sees a row that
+    was not checked on the host."""
+
+    def __init__(self, rows, geom):
+        self.rows, self.geom, self._dev = rows, tuple(geom), {}
+
+    def __len__(self):
+        return self.rows.shape[0]
+
+    def to(self, device):
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise _lib.FcdError('fcd_gan_pytorch_amd: the tile table goes to a CUDA/ROCm device, not %s (no CPU fallback)' % device)
+        if device not in self._dev:
+            self._dev[device] = torch.from_numpy(self.rows).to(device)
+        return self._dev[device]
+
+
+def validate_tile_rows(rows, W, H, pw, ph, padx, pady):
+    """Raise FcdError unless every (n,12) row keeps the kernels inside their buffers: read rectangle inside the (H,W) scene,
+    canvas window inside (ph,pw) and exactly as large as the read rectangle, owned rectangle inside the scene and, shifted by
+    the pad, inside the canvas; nothing negative."""
+    import numpy as np
+    r = np.asarray(rows)
+    if r.ndim != 2 or r.shape[1] != 12 or r.shape[0] == 0:
+        raise _lib.FcdError('tile table: expected (n,12) rows with n > 0, got shape %s' % (r.shape,))
+    r = r.astype(np.int64)
+    x0, y0, w, h, rx, ry, rw, rh, wx, wy, ww, wh = (r[:, k] for k in range(12))
+    checks = (
+        ('a negative entry', (r < 0).any(axis=1)),
+        ('the read rectangle leaves the scene', (rx + rw > W) | (ry + rh > H)),
+        ('the canvas window leaves the patch', (wx + ww > pw) | (wy + wh > ph)),
+        ('the canvas window and the read rectangle differ in size', (ww != rw) | (wh != rh)),
+        ('the owned rectangle leaves the scene', (x0 + w > W) | (y0 + h > H)),
+        ('the owned rectangle, shifted by the pad, leaves the patch', (padx + w > pw) | (pady + h > ph)),
+    )
+    for what, bad in checks:
+        if bad.any():
+            i = int(np.argmax(bad))
+            raise _lib.FcdError('tile table row %d: %s (row %s, scene %dx%d, patch %dx%d, pad %d,%d)'
+                                % (i, what, r[i].tolist(), W, H, pw, ph, padx, pady))
+
+
+def scene_tile_table(grid, items):
+    """The tile table of ``items`` on ``grid`` (a ``tiles.TileGrid``): built on the host from ``grid.slices`` -- the kernels add no
+    tiling arithmetic, so the reference's border rule stays in one place -- and validated there (:func:`validate_tile_rows`)
+    before anything is uploaded."""
+    import numpy as np
+    rows = np.array([sum((list(t) for t in grid.slices(int(i))), []) for i in items], dtype=np.int64).reshape(-1, 12)
+    geom = (grid.xsize, grid.ysize, grid.patch_size[0], grid.patch_size[1], grid.pad[0], grid.pad[1])
+    validate_tile_rows(rows, *geom)
+    return TileTable(np.ascontiguousarray(rows.astype(np.int32)), geom)
+
+
+def _scene_tensor(t, name, sample_type=None):
+    """A resident scene: contiguous device tensor of a supported sample type -> (tensor, sample type code)."""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise _lib.FcdError('fcd_gan_pytorch_amd: %s is on %s; the HIP path needs a CUDA/ROCm tensor (no CPU fallback)'
+                            % (name, t.device if torch.is_tensor(t) else type(t).__name__))
+    if sample_type is None:
+        sample_type = _SAMPLE_OF.get(t.dtype)
+    size = {SAMPLE_U8: 1, SAMPLE_U16: 2, SAMPLE_F32: 4}.get(sample_type)
+    if size is None or t.element_size() != size or (sample_type == SAMPLE_F32 and t.dtype != torch.float32):
+        raise _lib.FcdError('fcd_gan_pytorch_amd: %s must hold uint8, uint16 or float32 samples, got %s' % (name, t.dtype))
+    return t.contiguous(), sample_type
+
+
+def _table_for(table, W, H, pw=None, ph=None):
+    if not isinstance(table, TileTable):
+        raise _lib.FcdError('fcd_gan_pytorch_amd: pass the TileTable scene_tile_table() returns (it is validated on the host)')
+    if table.geom[:2] != (W, H) or (pw is not None and table.geom[2:4] != (pw, ph)):
+        raise _lib.FcdError('tile table was validated for scene %dx%d, patch %dx%d; used with scene %dx%d, patch %s'
+                            % (table.geom[:4] + (W, H, (pw, ph))))
+    return table
+
+
+@torch.no_grad()
+def scene_cut(scene_x, scene_y, table, ref=None, stats=None, want_valid=True, sample_type=None, ref_type=None, out=None):
+    """Cut the tiles of ``table`` out of the resident scene pair ``(C,H,W)`` (uint8 / uint16 / float32 samples; ``sample_type``
+    = SAMPLE_U16 for uint16 bits held in an int16 tensor) and the optional reference map ``(1,H,W)`` in one launch
+    (GDALDataset.__getitem__, data_utils.py:98-118).  ``stats`` = device float64 tensor of 4*C values (meanX, stdX, meanY,
+    stdY): normalise like the host path, bit-identically; None: plain ``float(v)``.
+    Returns ``(x, y, ref_tiles or None, valid or None)``: (n,C,ph,pw) / (n,1,ph,pw) float32, every element written (``out`` =
+    such a tuple of preallocated contiguous tensors to write into; no memset is needed)."""
+    sx, st = _scene_tensor(scene_x, 'scene_x', sample_type)
+    sy, st_y = _scene_tensor(scene_y, 'scene_y', sample_type)
+    if sx.dim() != 3 or sx.shape != sy.shape or st != st_y:
+        raise _lib.FcdError('scene_cut: the two scenes must be (C,H,W) tensors of one shape and sample type')
+    C, H, W = sx.shape
+    table = _table_for(table, W, H)
+    _, _, pw, ph, _, _ = table.geom
+    n = len(table)
+    r, rt = (None, 0)
+    if ref is not None:
+        r, rt = _scene_tensor(ref, 'reference map', ref_type)
+        if r.numel() != H * W:
+            raise _lib.FcdError("scene_cut: Reference sizes don't match image")
+    s = None
+    if stats is not None:
+        if not torch.is_tensor(stats) or not stats.is_cuda or stats.dtype != torch.float64 or stats.numel() != 4 * C:
+            raise _lib.FcdError('scene_cut: stats must be a device float64 tensor of 4*C values (meanX, stdX, meanY, stdY)')
+        s = stats.contiguous()
+    dev = sx.device
+    if out is None:
+        x = torch.empty((n, C, ph, pw), dtype=torch.float32, device=dev)
+        y = torch.empty_like(x)
+        rtile = torch.empty((n, 1, ph, pw), dtype=torch.float32, device=dev) if r is not None else None
+        valid = torch.empty((n, 1, ph, pw), dtype=torch.float32, device=dev) if want_valid else None
+    else:
+        x, y, rtile, valid = out
+        for t, shape, name in ((x, (n, C, ph, pw), 'x'), (y, (n, C, ph, pw), 'y'), (rtile, (n, 1, ph, pw), 'ref tiles'),
+                               (valid, (n, 1, ph, pw), 'valid')):
+            if t is not None and (_dev(t, 'out ' + name) is not t or tuple(t.shape) != shape or t.device != dev):
+                raise _lib.FcdError('scene_cut: out %s must be a contiguous %s float32 tensor on %s' % (name, shape, dev))
+        if (rtile is None) != (r is None):
+            raise _lib.FcdError('scene_cut: reference map and out reference tiles go together')
+    check(lib.fcd_scene_cut(_p(sx), _p(sy), st, _p(r), rt, C, H, W, _p(table.to(dev)), n, ph, pw, _p(s), _p(x), _p(y), _p(rtile),
+                            _p(valid), _stream()), 'fcd_scene_cut')
+    return x, y, rtile, valid
+
+
+def _counts_arg(counts, device):
+    if counts is None:
+        return None
+    if not counts.is_cuda or counts.dtype != torch.int64 or counts.numel() != 4 or not counts.is_contiguous():
+        raise _lib.FcdError('fcd_gan_pytorch_amd: counts must be a contiguous device int64 tensor of 4 elements')
+    if counts.device != device:
+        raise _lib.FcdError('fcd_gan_pytorch_amd: counts live on %s, the maps on %s' % (counts.device, device))
+    return counts
+
+
+@torch.no_grad()
+def scene_stitch(cmap, table, density, color, n=None, prob_thresh=0.5, gt_map=(1, 2), pre_map=(0, 1), write_color=True,
+                 ref=None, counts=None):
+    """Write the owned centres of the first ``n`` tiles of ``cmap`` (N,1,ph,pw) into the resident ``density`` / ``color`` maps
+    ((1,H,W) float32 device tensors, updated in place), colour-coded against the resident float32 reference ``ref`` ((1,H,W)
+    or None) and counted into ``counts`` (device int64[4], accumulated in place; cell order of Evaluator.add_batch_map)."""
+    cmap = _dev(cmap, 'cmap')
+    if cmap.dim() != 4 or cmap.shape[1] != 1:
+        raise _lib.FcdError('scene_stitch: cmap must be (N,1,ph,pw), got %s' % (tuple(cmap.shape),))
+    N, _, ph, pw = cmap.shape
+    for t, name in ((density, 'density'), (color, 'color')):
+        if _dev(t, name) is not t:
+            raise _lib.FcdError('scene_stitch: %s must be contiguous (it is written in place)' % name)
+    H, W = density.shape[-2:]
+    if density.numel() != H * W or tuple(color.shape) != tuple(density.shape):
+        raise _lib.FcdError('scene_stitch: density and color must be (1,H,W) maps of one shape')
+    table = _table_for(table, W, H, pw, ph)
+    n = len(table) if n is None else int(n)
+    if not 0 < n <= min(len(table), N):
+        raise _lib.FcdError('scene_stitch: n = %d with %d table rows and %d tiles' % (n, len(table), N))
+    r = None
+    if ref is not None:
+        r = _dev(ref, 'reference map')
+        if r.numel() != H * W:
+            raise _lib.FcdError("scene_stitch: Reference sizes don't match image")
+    counts = _counts_arg(counts, cmap.device)
+    padx, pady = table.geom[4:6]
+    check(lib.fcd_scene_stitch(_p(cmap), _p(table.to(cmap.device)), n, ph, pw, padx, pady, float(prob_thresh), float(gt_map[0]),
+                               float(gt_map[1]), float(pre_map[0]), float(pre_map[1]), 1 if write_color else 0, _p(r), H, W,
+                               _p(density), _p(color), _p(counts), _stream()), 'fcd_scene_stitch')
+    return density, color
+
+
+@torch.no_grad()
+def tile_confusion(cmap, ref_tiles, rects, counts, prob_thresh=0.5, gt_map=(0, 1), pre_map=(0, 1)):
+    """counts[2*i+j] += #(ref_tiles == gt_map[i] and (cmap > prob_thresh) == pre_map[j]) over rows [r0,r1) x columns [c0,c1) of
+    every tile; ``rects`` = host sequence of (r0, r1, c0, c1) per tile (``TileGrid.eff_range``), validated here before upload.
+    ``counts``: device int64[4], accumulated in place."""
+    import numpy as np
+    cmap, ref_tiles = _dev(cmap, 'cmap'), _dev(ref_tiles, 'reference tiles')
+    if cmap.dim() != 4 or cmap.shape[1] != 1 or cmap.shape != ref_tiles.shape:
+        raise _lib.FcdError('tile_confusion: cmap and reference tiles must both be (N,1,ph,pw)')
+    N, _, ph, pw = cmap.shape
+    rc = np.asarray(rects, dtype=np.int64).reshape(-1, 4)
+    if not 0 < rc.shape[0] <= N:
+        raise _lib.FcdError('tile_confusion: %d rectangles for %d tiles' % (rc.shape[0], N))
+    if (rc < 0).any() or (rc[:, 1] > ph).any() or (rc[:, 3] > pw).any() or (rc[:, 0] > rc[:, 1]).any() or (rc[:, 2] > rc[:, 3]).any():
+        raise _lib.FcdError('tile_confusion: a rectangle leaves the (%d,%d) tile' % (ph, pw))
+    counts = _counts_arg(counts, cmap.device)
+    if counts is None:
+        raise _lib.FcdError('tile_confusion: counts is required')
+    rd = torch.from_numpy(np.ascontiguousarray(rc.astype(np.int32))).to(cmap.device)
+    check(lib.fcd_tile_confusion(_p(cmap), _p(ref_tiles), _p(rd), rc.shape[0], ph, pw, float(prob_thresh), float(gt_map[0]),
+                                 float(gt_map[1]), float(pre_map[0]), float(pre_map[1]), _p(counts), _stream()),
+          'fcd_tile_confusion')
+    return counts
+
+
 # ------------------------------------------------------------------------ losses
 class _MaskedSums(torch.autograd.Function):
     """out[2N] = {num[n], wsum[n]} of include/fcdgan_hip.h:fcd_masked_recon_fwd."""

@@ -1,0 +1,254 @@
+// Device-resident scene inference: cut tiles out of a scene pair that lives in HBM, stitch the owned centres of the
+// network's density tiles back into scene-sized maps, colour-code them and count the 2x2 confusion matrix -- the data
+// movement around the Segmentor in the reference's inference loop (data_utils.py:98-118,205-213,230-236,
+// Demo_RSSS.py:345-354,457-491, CommonFunc.py:59-75, metrics.py:67-72).
+//
+// All three kernels are HBM-bound copies with integer bookkeeping; the only floating-point arithmetic is the fp64
+// normalisation of fcd_normalize_tiles.  Geometry comes from a TILE TABLE, int32 (n,12): every row is
+// TileGrid.slices(item) flattened -- own x0,y0,w,h | read rx,ry,rw,rh | canvas wx,wy,ww,wh.  The kernels add no tiling
+// arithmetic of their own (the reference's border rule lives in ONE place, TileGrid), and they trust the table: the
+// caller validates every row on the host before upload (_ops.scene_tile_table).
+//
+// Work split, all kernels: one wavefront per canvas ROW, lanes along the row -- 64 consecutive dwords = one 256-B
+// wave instruction per load / store, whatever the scene width and x0 are (no alignment assumed anywhere, so no vector
+// accesses: rows start at arbitrary element offsets in the scene and at r*pw in the canvases).  The grid is 2-D: x = the
+// canvas rows in groups of one per wavefront, y = the planes (cut) or tiles (stitch, confusion) behind a grid-stride loop
+// capped at the y limit, so any n*planes fits; all offsets into the scene and the canvases are 64-bit.  Wave index, plane
+// and table row are wave-uniform (readfirstlane): the decode runs on the scalar unit and the table comes in by scalar loads.
+#include "common.h"
+
+enum { T_X0 = 0, T_Y0, T_W, T_H, T_RX, T_RY, T_RW, T_RH, T_WX, T_WY, T_WW, T_WH, T_COLS };
+
+constexpr int kBlock = 256, kWaves = kBlock / FCD_WAVE;                // cut: 4 canvas rows per workgroup
+// The counting kernels end in one atomic per counter per WORKGROUP, all on the caller's four counters (one cache line):
+// 16 rows per workgroup and at most kCountBlocks workgroups (2 per CU = every wave slot of the chip) keep that to a few
+// thousand same-line atomics per launch however large the batch is; further tiles go round the grid-stride loop.
+constexpr int kCountBlock = 1024, kCountWaves = kCountBlock / FCD_WAVE, kCountBlocks = 512;
+constexpr int kMaxGridY = 65535;       // more planes / tiles than that go round the grid-stride loop
+
+static inline dim3 row_grid(int ph, long long units) { return dim3(cdiv(ph, kWaves), (unsigned)std::min<long long>(units, kMaxGridY)); }
+static inline dim3 count_grid(int ph, int n) {
+  const int gx = cdiv(ph, kCountWaves);
+  return dim3(gx, (unsigned)std::min(n, std::max(1, kCountBlocks / gx)));
+}
+// canvas row of this wavefront, in a scalar register
+template <int WAVES>
+__device__ __forceinline__ int wave_row() { return blockIdx.x * WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+
+// A scene sample as float: exact for all three sample types (uint8 / uint16 fit the 24-bit significand).
+__device__ __forceinline__ float load_sample(const void* __restrict__ base, long long idx, int type) {
+  if (type == FCD_SAMPLE_U8) return (float)((const uint8_t*)base)[idx];
+  if (type == FCD_SAMPLE_U16) return (float)((const uint16_t*)base)[idx];
+  return ((const float*)base)[idx];
+}
+
+// ---- cut -------------------------------------------------------------------------------------------------------
+// planes of one tile: C of x, C of y, [ref], [valid]; one wave per (tile, plane, canvas row).
+__global__ __launch_bounds__(kBlock) void fcd_scene_cut_kernel(
+    const void* __restrict__ sx, const void* __restrict__ sy, int stype, const void* __restrict__ sref, int rtype, int C,
+    long long H, long long W, const int32_t* __restrict__ table, int units, int ph, int pw,
+    const double* __restrict__ stats, float* __restrict__ x, float* __restrict__ y, float* __restrict__ ref_tiles,
+    float* __restrict__ valid) {
+  const int lane = threadIdx.x & (FCD_WAVE - 1);
+  const unsigned planes = 2 * C + (ref_tiles ? 1 : 0) + (valid ? 1 : 0);
+  const int j = wave_row<kWaves>();
+  if (j >= ph) return;
+  for (unsigned pl = blockIdx.y; pl < (unsigned)units; pl += gridDim.y) {      // units = n * planes <= INT_MAX (checked by the host)
+    const long long t = pl / planes;
+    const int q = (int)(pl - (unsigned)t * planes);
+    const int32_t* __restrict__ row = table + t * T_COLS;
+    const int rx = row[T_RX], ry = row[T_RY], wx = row[T_WX], wy = row[T_WY], ww = row[T_WW], wh = row[T_WH];
+    const bool in_rows = j >= wy && j < wy + wh;
+    // which plane: source, sample type, destination, per-band statistics
+    const void* src;
+    float* dst;
+    int type = stype, c = 0;
+    bool norm = false, ones = false;
+    if (q < C) {
+      src = sx; c = q; dst = x + ((t * C + c) * ph + j) * pw; norm = stats != nullptr;
+    } else if (q < 2 * C) {
+      src = sy; c = q - C; dst = y + ((t * C + c) * ph + j) * pw; norm = stats != nullptr;
+    } else if (ref_tiles && q == 2 * C) {
+      src = sref; type = rtype; dst = ref_tiles + (t * ph + j) * pw;
+    } else {
+      src = nullptr; ones = true; dst = valid + (t * ph + j) * pw;
+    }
+    double mean = 0.0, stdv = 1.0;
+    if (norm) {          // stats = meanX[C], stdX[C], meanY[C], stdY[C]
+      const double* __restrict__ s = stats + (q < C ? 0 : 2 * C);
+      mean = s[c]; stdv = s[C + c];
+    }
+    // first sample of the scene row this canvas row reads, shifted so that canvas column i reads element i
+    const long long sbase = ((long long)c * H + (ry + (j - wy))) * W + (rx - wx);
+    for (int i = lane; i < pw; i += FCD_WAVE) {
+      float v = 0.f;
+      if (in_rows && i >= wx && i < wx + ww) {
+        if (ones) {
+          v = 1.f;
+        } else {
+          v = load_sample(src, sbase + i, type);
+          if (norm) v = (float)(((double)v - mean) / stdv);
+        }
+      }
+      dst[i] = v;
+    }
+  }
+}
+
+// ---- counting, shared by stitch and tile_confusion -----------------------------------------------------------------
+struct SceneCountArgs {
+  float thresh, gt0, gt1, pre0, pre1;
+};
+
+// cmap > prob_thresh in fp32 (a NaN density is "not changed", as NaN > t is false)
+__device__ __forceinline__ float threshold(float p, float thresh) { return p > thresh ? 1.f : 0.f; }
+
+// Evaluator.add_batch_map's four cells, counts[2 * i + j] += (ref == gt_i && pre == pre_j): one ballot + popcount per cell over
+// the wavefront (the ballot is 64 bits wide).  Every lane of the wave must call this (inactive pixels pass live = false); the
+// running totals are wave-uniform.
+__device__ __forceinline__ void count_cells(bool live, float ref, float pre, const SceneCountArgs& a, unsigned long long cnt[4]) {
+  cnt[0] += __popcll(__ballot(live && ref == a.gt0 && pre == a.pre0));
+  cnt[1] += __popcll(__ballot(live && ref == a.gt0 && pre == a.pre1));
+  cnt[2] += __popcll(__ballot(live && ref == a.gt1 && pre == a.pre0));
+  cnt[3] += __popcll(__ballot(live && ref == a.gt1 && pre == a.pre1));
+}
+
+// wave totals -> workgroup totals in LDS -> ONE ordinary global atomicAdd per counter per workgroup (integer sums: the result does
+// not depend on the order the workgroups arrive in)
+__device__ __forceinline__ void flush_counts(const unsigned long long cnt[4], unsigned long long* __restrict__ counts) {
+  __shared__ unsigned long long part[kCountWaves][4];
+  const int lane = threadIdx.x & (FCD_WAVE - 1), w = threadIdx.x >> 6;
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) part[w][k] = cnt[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    unsigned long long s = 0;
+#pragma unroll
+    for (int k = 0; k < kCountWaves; ++k) s += part[k][threadIdx.x];
+    if (s) atomicAdd(counts + threadIdx.x, s);
+  }
+}
+
+// ---- stitch ------------------------------------------------------------------------------------------------------
+// one wave per (tile, canvas row j < ph); rows j >= h of a clipped tile have nothing to write.
+__global__ __launch_bounds__(kCountBlock) void fcd_scene_stitch_kernel(
+    const float* __restrict__ cmap, const int32_t* __restrict__ table, int n, int ph, int pw, int padx, int pady,
+    SceneCountArgs a, int write_color, const float* __restrict__ ref, long long W, float* __restrict__ density,
+    float* __restrict__ color, unsigned long long* __restrict__ counts) {
+  const int lane = threadIdx.x & (FCD_WAVE - 1);
+  const int j = wave_row<kCountWaves>();
+  unsigned long long cnt[4] = {0, 0, 0, 0};
+  for (long long t = blockIdx.y; t < n; t += gridDim.y) {   // no early return: every wave reaches the barrier in flush_counts
+    const int32_t* __restrict__ row = table + t * T_COLS;
+    const int x0 = row[T_X0], y0 = row[T_Y0], w = row[T_W], h = row[T_H];
+    if (j >= h) continue;                                    // wave-uniform (h <= ph - pady: rows past the canvas end here too)
+    const float* __restrict__ src = cmap + ((t * ph) + pady + j) * pw + padx;
+    const long long obase = (long long)(y0 + j) * W + x0;
+    for (int i0 = 0; i0 < w; i0 += FCD_WAVE) {               // wave-uniform trip count: every lane reaches the ballots
+      const int i = i0 + lane;
+      const bool live = i < w;
+      float p = 0.f, g = 0.f;
+      if (live) {
+        p = src[i];
+        if (ref) g = ref[obase + i];
+      }
+      const float pre = threshold(p, a.thresh);
+      float code = 0.f;
+      if (write_color && ref) {                              // write_changemap_gdal's assignment order: the later rule wins
+        if (pre == a.pre0 && g == a.gt1) code = 1.f;         // miss
+        if (pre == a.pre1 && g == a.gt0) code = 2.f;         // false detection
+        if (pre == a.pre1 && g == a.gt1) code = 3.f;         // true detection
+      } else if (pre == a.pre1) {
+        code = 1.f;
+      }
+      if (live) {
+        density[obase + i] = p;
+        color[obase + i] = code;
+      }
+      if (ref && counts) count_cells(live, g, pre, a, cnt);
+    }
+  }
+  if (ref && counts) flush_counts(cnt, counts);
+}
+
+// ---- confusion counts over tiles (the training loops' metric) --------------------------------------------------------------
+// rects: int32 (n,4) = r0,r1,c0,c1 (TileGrid.eff_range); one wave per (tile, canvas row), rows outside [r0,r1) skipped.
+__global__ __launch_bounds__(kCountBlock) void fcd_tile_confusion_kernel(
+    const float* __restrict__ cmap, const float* __restrict__ ref_tiles, const int32_t* __restrict__ rects, int n,
+    int ph, int pw, SceneCountArgs a, unsigned long long* __restrict__ counts) {
+  const int lane = threadIdx.x & (FCD_WAVE - 1);
+  const int j = wave_row<kCountWaves>();
+  unsigned long long cnt[4] = {0, 0, 0, 0};
+  for (long long t = blockIdx.y; t < n; t += gridDim.y) {
+    const int32_t* __restrict__ rc = rects + t * 4;
+    const int r0 = rc[0], r1 = rc[1], c0 = rc[2], c1 = rc[3];
+    if (j < r0 || j >= r1) continue;                         // wave-uniform (r1 <= ph)
+    const long long base = (t * ph + j) * pw;
+    for (int i0 = c0; i0 < c1; i0 += FCD_WAVE) {
+      const int i = i0 + lane;
+      const bool live = i < c1;
+      float p = 0.f, g = 0.f;
+      if (live) {
+        p = cmap[base + i];
+        g = ref_tiles[base + i];
+      }
+      count_cells(live, g, threshold(p, a.thresh), a, cnt);
+    }
+  }
+  flush_counts(cnt, counts);
+}
+
+static bool sample_type_ok(int t) { return t == FCD_SAMPLE_U8 || t == FCD_SAMPLE_U16 || t == FCD_SAMPLE_F32; }
+
+
+extern "C" int fcd_scene_cut(const void* scene_x, const void* scene_y, int sample_type, const void* ref, int ref_type, int C,
+                             int H, int W, const int32_t* table, int n, int ph, int pw, const double* stats, float* x,
+                             float* y, float* ref_tiles, float* valid, void* stream) {
+  FCD_CHECK_ARG(scene_x && scene_y && table && x && y && C > 0 && H > 0 && W > 0 && n > 0 && ph > 0 && pw > 0,
+                "fcd_scene_cut: bad arguments");
+  FCD_CHECK_ARG(sample_type_ok(sample_type), "fcd_scene_cut: sample type %d (0 uint8, 1 uint16, 2 float32)", sample_type);
+  FCD_CHECK_ARG((ref != nullptr) == (ref_tiles != nullptr), "fcd_scene_cut: reference map and reference tiles go together");
+  FCD_CHECK_ARG(!ref || sample_type_ok(ref_type), "fcd_scene_cut: reference sample type %d", ref_type);
+  const int planes = 2 * C + (ref_tiles ? 1 : 0) + (valid ? 1 : 0);
+  const long long units = (long long)n * planes;
+  FCD_CHECK_ARG(units <= INT32_MAX, "fcd_scene_cut: %d tiles x %d planes exceed 2^31 - 1", n, planes);
+  const long long rows = units * ph;
+  const double in_bytes = sample_type == FCD_SAMPLE_U8 ? 1.0 : sample_type == FCD_SAMPLE_U16 ? 2.0 : 4.0;
+  FcdProfScope prof(FCD_K_MISC, (hipStream_t)stream, 0.0, (double)rows * pw * 4.0 + 2.0 * n * C * ph * pw * in_bytes);
+  hipLaunchKernelGGL(fcd_scene_cut_kernel, row_grid(ph, units), dim3(kBlock), 0, (hipStream_t)stream, scene_x, scene_y,
+                     sample_type, ref, ref_type, C, (long long)H, (long long)W, table, (int)units, ph, pw, stats, x, y, ref_tiles,
+                     valid);
+  FCD_LAUNCH_CHECK("fcd_scene_cut");
+  return FCD_OK;
+}
+
+extern "C" int fcd_scene_stitch(const float* cmap, const int32_t* table, int n, int ph, int pw, int padx, int pady,
+                                float thresh, float gt0, float gt1, float pre0, float pre1, int write_color,
+                                const float* ref_scene, int H, int W, float* density, float* color,
+                                unsigned long long* counts, void* stream) {
+  FCD_CHECK_ARG(cmap && table && density && color && n > 0 && ph > 0 && pw > 0 && H > 0 && W > 0 && padx >= 0 && pady >= 0 &&
+                    2 * padx < pw && 2 * pady < ph,
+                "fcd_scene_stitch: bad arguments");
+  const long long rows = (long long)n * ph;
+  FcdProfScope prof(FCD_K_MISC, (hipStream_t)stream, 0.0, (double)rows * pw * (ref_scene ? 16.0 : 12.0));
+  const SceneCountArgs a{thresh, gt0, gt1, pre0, pre1};
+  hipLaunchKernelGGL(fcd_scene_stitch_kernel, count_grid(ph, n), dim3(kCountBlock), 0, (hipStream_t)stream, cmap, table, n, ph, pw,
+                     padx, pady, a, write_color, ref_scene, (long long)W, density, color, counts);
+  FCD_LAUNCH_CHECK("fcd_scene_stitch");
+  return FCD_OK;
+}
+
+extern "C" int fcd_tile_confusion(const float* cmap, const float* ref_tiles, const int32_t* rects, int n, int ph, int pw,
+                                  float thresh, float gt0, float gt1, float pre0, float pre1, unsigned long long* counts,
+                                  void* stream) {
+  FCD_CHECK_ARG(cmap && ref_tiles && rects && counts && n > 0 && ph > 0 && pw > 0, "fcd_tile_confusion: bad arguments");
+  const long long rows = (long long)n * ph;
+  FcdProfScope prof(FCD_K_MISC, (hipStream_t)stream, 0.0, (double)rows * pw * 8.0);
+  const SceneCountArgs a{thresh, gt0, gt1, pre0, pre1};
+  hipLaunchKernelGGL(fcd_tile_confusion_kernel, count_grid(ph, n), dim3(kCountBlock), 0, (hipStream_t)stream, cmap, ref_tiles,
+                     rects, n, ph, pw, a, counts);
+  FCD_LAUNCH_CHECK("fcd_tile_confusion");
+  return FCD_OK;
+}

@@ -76,11 +76,12 @@ def demo_usss(scene_x, scene_y, ref=None, device='cuda', patch_size=(220, 220), 
               epochs_g=50, epochs_s=50, epochs_joint=100, batch_size=10, learning_rate=2e-4,
               perception_weight=0.4, l1_weight=0.65, ssim_weight=0, perception_perBand=True,
               prob_thresh=0.5, gt_map=(1, 2), pre_map=(0, 1), seed=0, out_density=None, out_color=None,
-              log=None, allow_seeded=False, stats_txt=None, save_s=None, save_g=None, ragged='pad'):
+              log=None, allow_seeded=False, stats_txt=None, save_s=None, save_g=None, ragged='pad', resident_inference=False):
     """Demo_USSS.py:29-501: G pre-train -> S pre-train -> joint training -> inference with centre write-back, with the
     reference's LR schedules (Demo_USSS.py:133,201,298-299) and per-tile dataset statistics (:88-95).
     ``scene_x/scene_y/ref``: (bands,H,W) arrays or TIFF paths; ``save_s`` / ``save_g``: ``.pkl`` paths
-    (Demo_USSS.py:477-481).  ``batch_size`` is per rank under data parallelism.
+    (Demo_USSS.py:477-481).  ``batch_size`` is per rank under data parallelism.  ``resident_inference=True`` runs the final
+    inference with the scene pair and the maps resident on the device (``infer_scene_resident``: same maps and scores).
     Returns dict(netS, netG, density (1,H,W) float32, color (1,H,W), evaluator, history, vgg_pretrained)."""
     dev = torch.device(device)
     if isinstance(scene_x, str):
@@ -139,7 +140,12 @@ def demo_usss(scene_x, scene_y, ref=None, device='cuda', patch_size=(220, 220), 
             log('joint epoch %d loss %.4f' % (ep + 1, hist['joint'][-1]))
 
     dp.sync_buffers((netS, netG))            # one set of BatchNorm statistics for the stitched map AND the checkpoint
-    res = infer_scene(netS, ds, dev, batch_size=batch_size, prob_thresh=prob_thresh, gt_map=gt_map, pre_map=pre_map)
+    if resident_inference:
+        scene = tiles.ResidentScene(scene_x, scene_y, ref, patch_size, overlap_padding, stats=stats, device=dev)
+        res = infer_scene_resident(netS, scene, dev, batch_size=batch_size, prob_thresh=prob_thresh, gt_map=gt_map,
+                                   pre_map=pre_map)
+    else:
+        res = infer_scene(netS, ds, dev, batch_size=batch_size, prob_thresh=prob_thresh, gt_map=gt_map, pre_map=pre_map)
     if out_density and dp.world_info()[0] == 0:
         tiles.write_tiff(out_density, res['density'])
     if out_color and dp.world_info()[0] == 0:
@@ -191,6 +197,53 @@ def infer_scene(netS, ds, device, batch_size=10, prob_thresh=0.5, gt_map=(1, 2),
         density, color = (a.copy() for a in both.cpu().numpy())
     netS.train(was_training)
     return dict(density=density, color=color, evaluator=acc)
+
+
+@torch.no_grad()
+def infer_scene_resident(netS, scene, device, batch_size=10, prob_thresh=0.5, gt_map=(1, 2), pre_map=(0, 1), eval_mode=True,
+                         raw=False):
+    """``infer_scene`` with everything but the network's weights of the loop kept on the device: ``scene`` is a
+    ``tiles.ResidentScene`` (single scene); tiles are cut by ``fcd_scene_cut``, the owned centres written into device maps,
+    colour-coded and counted by ``fcd_scene_stitch`` -- two launches per batch around the Segmentor, no host tile loop, ONE
+    device-to-host copy per map at the end.  Same batches as ``infer_scene`` (``dp.RankStridedBatches(shuffle=False)``, padded
+    duplicates cut and inferred but not stitched), same data-parallel rule (each rank stitches its own tiles into zeroed maps,
+    maps and counts are summed across ranks on the device), same returned dict -- bit for bit, since the input tiles are.
+    ``raw=True`` cuts plain samples and runs ``steps.infer_density_raw`` (NORMALIZE folded into the first convolution): eval
+    mode only, density within rounding of the normalised path."""
+    if not isinstance(scene, tiles.ResidentScene):
+        raise TypeError('infer_scene_resident takes a tiles.ResidentScene (one scene pair), got %s' % type(scene).__name__)
+    if raw and not eval_mode:
+        raise RuntimeError('raw=True folds NORMALIZE into the first convolution: eval mode only (Segmentor.forward_raw)')
+    if raw and scene.stats is None:
+        raise RuntimeError('raw=True needs the scene statistics (ResidentScene(stats=...))')
+    from . import _ops as ops
+    dev = torch.device(device)
+    if eval_mode:
+        dp.sync_buffers((netS,))
+    was_training = netS.training
+    netS.train(not eval_mode)
+    grid = scene.grid
+    density, color = scene.new_maps()
+    acc = metrics.Evaluator(2)
+    counts = acc.device_counts(dev) if scene.ref is not None else None
+    sampler = dp.RankStridedBatches(len(grid), batch_size, seed=0, shuffle=False)
+    for b, items in enumerate(sampler):
+        real = len(items) - sampler.pads[b]                    # padded duplicates belong to another rank
+        table = ops.scene_tile_table(grid, items)
+        x, y, _, valid = scene.cut(table, raw=raw)
+        if raw:
+            cmap, _ = steps.infer_density_raw(netS, x, y, valid, scene.stats, prob_thresh)
+        else:
+            cmap, _ = steps.infer_density(netS, x, y, prob_thresh)
+        if real > 0:
+            ops.scene_stitch(cmap, table, density, color, n=real, prob_thresh=prob_thresh, gt_map=gt_map, pre_map=pre_map,
+                             write_color=True, ref=scene.ref, counts=counts)
+    if dp.exchanging():
+        both = torch.stack([density, color])
+        dp.sum_counts(both)                                    # the evaluator's counts are summed in Evaluator._sync
+        density, color = both[0], both[1]
+    netS.train(was_training)
+    return dict(density=density.cpu().numpy(), color=color.cpu().numpy(), evaluator=acc)
 
 
 def _valid_centres(dataset, like, items, real):

@@ -66,6 +66,21 @@ class Evaluator:
         c = torch.stack(cells).to(torch.int64)
         self._dev_counts = c if self._dev_counts is None else self._dev_counts + c
 
+    def device_counts(self, device):
+        """The int64[4] device counter the HIP kernels accumulate into in place (``fcd_tile_confusion``, ``fcd_scene_stitch``),
+        allocated on first use; ``add_batch_map`` adds into the same tensor."""
+        if self._dev_counts is None:
+            self._dev_counts = torch.zeros(4, dtype=torch.int64, device=device)
+        return self._dev_counts
+
+    def add_tiles(self, ref_tiles, cmap, rects, prob_thresh=0.5, gt_map=(0, 1), pre_map=(0, 1)):
+        """``add_batch_map(ref_tiles, cmap > prob_thresh, gt_map, pre_map, valid=<rects>)`` as ONE kernel: the density tiles
+        ``cmap`` (N,1,H,W) are thresholded, compared with the reference tiles and counted over ``rects`` = (r0, r1, c0, c1) per
+        tile (``TileGrid.eff_range``; fewer rects than tiles: the trailing padded duplicates are left out)."""
+        from . import _ops as ops
+        assert len(gt_map) == len(pre_map) == self.num_class
+        ops.tile_confusion(cmap, ref_tiles, rects, self.device_counts(cmap.device), prob_thresh, gt_map, pre_map)
+
     def _sync(self):
         if self._dev_counts is not None:
             c = self._dev_counts

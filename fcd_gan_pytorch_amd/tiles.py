@@ -302,6 +302,71 @@ class RawTiles(torch.utils.data.Dataset):
         return self.ds.raw_item(item)
 
 
+class ResidentScene:
+    """A bi-temporal scene pair (+ optional reference map) that lives in device memory for a whole inference pass: uploaded
+    ONCE in its own sample type (uint8 / uint16 / float32 -- a uint16 scene is half the bytes of its fp32 tiles), cut into
+    the tiles of ``PairTileDataset`` on the device (``_ops.scene_cut``: same values bit for bit, no host loop, no pinned
+    staging).  The reference map goes up as float32, the form the stitch kernel compares in.  Single scene only."""
+
+    def __init__(self, scene_x, scene_y, ref=None, patch_size=(200, 200), overlap_padding=(10, 10), stats=None, device='cuda'):
+        from . import _ops as ops
+        if isinstance(scene_x, str):
+            scene_x = read_tiff(scene_x)
+        if isinstance(scene_y, str):
+            scene_y = read_tiff(scene_y)
+        if isinstance(ref, str):
+            ref = read_tiff(ref)
+        scene_x, scene_y = np.asarray(scene_x), np.asarray(scene_y)
+        if scene_x.shape != scene_y.shape or scene_x.ndim != 3:
+            raise ValueError("Image sizes don't match")
+        if scene_x.dtype != scene_y.dtype or scene_x.dtype not in (np.uint8, np.uint16, np.float32):
+            raise ops._lib.FcdError('ResidentScene: both scenes must be uint8, uint16 or float32 arrays of one type, got %s / %s'
+                                    % (scene_x.dtype, scene_y.dtype))
+        if ref is not None and (ref.shape[0] != 1 or ref.shape[1:] != scene_x.shape[1:]):
+            raise ValueError("Reference sizes don't match image")
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise ops._lib.FcdError('ResidentScene lives on a CUDA/ROCm device, not %s (no CPU fallback)' % self.device)
+        self.sample_type = {1: ops.SAMPLE_U8, 2: ops.SAMPLE_U16, 4: ops.SAMPLE_F32}[scene_x.dtype.itemsize]
+
+        def up(a):          # uint16 samples travel as int16 bits (same bytes; the kernel reads them as uint16)
+            a = np.ascontiguousarray(a)
+            return torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(self.device)
+        self.x, self.y = up(scene_x), up(scene_y)
+        self.ref = None if ref is None else torch.from_numpy(np.ascontiguousarray(ref, dtype=np.float32)).to(self.device)
+        self.grid = TileGrid(scene_x.shape[2], scene_x.shape[1], patch_size, overlap_padding)
+        self.bands = scene_x.shape[0]
+        self.stats = stats            # (meanX, stdX, meanY, stdY) per band, NORMALIZE semantics (as PairTileDataset)
+        self._stats_dev = None
+        if stats is not None:
+            s = np.stack([np.asarray(v, dtype=np.float64).reshape(-1) for v in stats])
+            if s.shape != (4, self.bands):
+                raise ops._lib.FcdError("ResidentScene: The input channel doesn't match the stats list")   # CommonFunc.py:212
+            self._stats_dev = torch.from_numpy(np.ascontiguousarray(s)).to(self.device)
+
+    def __len__(self):
+        return len(self.grid)
+
+    def table(self, items):
+        from . import _ops as ops
+        return items if isinstance(items, ops.TileTable) else ops.scene_tile_table(self.grid, items)
+
+    def cut(self, items, raw=False):
+        """``(x, y, ref, valid)`` of the tiles ``items`` (indices or a tile table), all on the device: x, y as
+        ``PairTileDataset.__getitem__`` returns them (normalised with ``stats`` when given) or, with ``raw=True``, as
+        ``raw_item`` does (plain samples -- for ``Segmentor.forward_raw``); ``ref`` (None without a reference map) and the
+        ``valid`` window mask are (n,1,py,px)."""
+        from . import _ops as ops
+        return ops.scene_cut(self.x, self.y, self.table(items), ref=self.ref, stats=None if raw else self._stats_dev,
+                             sample_type=self.sample_type)
+
+    def new_maps(self):
+        """Zeroed ``density`` and ``color`` maps, (1,H,W) float32 on the device."""
+        shape = (1, self.grid.ysize, self.grid.xsize)
+        return (torch.zeros(shape, dtype=torch.float32, device=self.device),
+                torch.zeros(shape, dtype=torch.float32, device=self.device))
+
+
 # ------------------------------------------------------------------------ dataset statistics
 def _valid(x):
     """Valid-pixel mask of a patch: pixels whose band sum is non-zero (nodata / zero padding excluded,

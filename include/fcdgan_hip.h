@@ -406,6 +406,46 @@ int fcd_masked_stack_bwd(const float* dz, const float* s0, const float* s1, cons
 int fcd_normalize_tiles(const float* x, const float* valid, const double* mean, const double* stdv, float* out,
                         int N, int C, int HW, void* stream);
 
+/* ---- device-resident scene inference (csrc/scene.hip) ------------------------
+ * The scene pair, the reference map and the output maps stay in device memory for a whole inference pass; these three
+ * entry points are the data movement around the Segmentor.  Geometry travels as a TILE TABLE: device int32 (n,12), row =
+ * TileGrid.slices(item) flattened = own x0,y0,w,h | read rx,ry,rw,rh | canvas wx,wy,ww,wh (data_utils.py:57-70,142-176).
+ * The kernels add no tiling arithmetic and do NOT range-check the rows: the caller validates the table on the host
+ * (read rectangle inside the scene, canvas window inside (ph,pw) and as large as the read rectangle, owned rectangle
+ * inside the scene and, shifted by the pad, inside the canvas) before uploading it.  Scene offsets are 64-bit. */
+#define FCD_SAMPLE_U8 0
+#define FCD_SAMPLE_U16 1
+#define FCD_SAMPLE_F32 2
+/* GDALDataset.__getitem__, data_utils.py:98-118 (read block -> 'enhance' -> zero-embedded canvas): cuts n tiles out of
+ * scene_x / scene_y (C*H*W samples of sample_type each) and, optionally, out of ref (H*W samples of ref_type; ref and
+ * ref_tiles both NULL or both given) in ONE launch.  x, y: n*C*ph*pw floats; ref_tiles, valid (optional): n*ph*pw floats.
+ * Inside the canvas window (wx,wy,ww,wh) an element is float((double(v) - mean[c]) / std[c]) when stats is given
+ * (4*C doubles on the device: meanX, stdX, meanY, stdY -- the arithmetic of fcd_normalize_tiles, bit-identical to the
+ * host path) and float(v) otherwise; ref_tiles are never normalised; valid is 1 there.  EVERY other canvas element is
+ * written as 0: the caller does no memset. */
+int fcd_scene_cut(const void* scene_x, const void* scene_y, int sample_type, const void* ref, int ref_type, int C, int H,
+                  int W, const int32_t* table, int n, int ph, int pw, const double* stats, float* x, float* y,
+                  float* ref_tiles, float* valid, void* stream);
+/* The per-batch tail of the inference loops, Demo_RSSS.py:345-354,457-491 with the centre write-back of
+ * data_utils.py:205-213,230-236, write_changemap_gdal CommonFunc.py:59-75 and Evaluator.add_batch_map metrics.py:67-72:
+ * for every owned-centre pixel of the first n tiles of cmap (n*ph*pw floats), p = cmap[t][pady + j][padx + i]:
+ *   density[y0 + j][x0 + i] = p;  pre = p > thresh ? 1 : 0  (fp32 compare; a NaN is written through and counts as 0);
+ *   color[..] = 1 miss (pre == pre0 && ref == gt1), 2 false detection (pre == pre1 && ref == gt0), 3 true detection
+ *   (pre == pre1 && ref == gt1), later rule wins, else 0 -- or, with write_color == 0 or ref_scene == NULL, 1 where
+ *   pre == pre1;  counts[2 * i + j] += (ref == gt_i && pre == pre_j)  when ref_scene and counts are given (a reference
+ *   value that is neither gt0 nor gt1 lands in no cell).
+ * ref_scene (optional), density, color: H*W floats.  counts: 4 unsigned 64-bit integers owned by the caller, ACCUMULATED
+ * across calls (one global atomic add per counter per workgroup; integer sums, so runs are bit-identical). */
+int fcd_scene_stitch(const float* cmap, const int32_t* table, int n, int ph, int pw, int padx, int pady, float thresh,
+                     float gt0, float gt1, float pre0, float pre1, int write_color, const float* ref_scene, int H, int W,
+                     float* density, float* color, unsigned long long* counts, void* stream);
+/* The same counting for the training loops (Demo_RSSS.py:345-354 over OSCD_Dataset_RSS.EffRange, data_utils.py:390-400,
+ * metrics.py:67-72) on reference TILES: counts[2 * i + j] += (ref_tiles == gt_i && (cmap > thresh) == pre_j) over rows
+ * [r0,r1) x columns [c0,c1) of every tile, rects = device int32 (n,4) of r0,r1,c0,c1 inside (ph,pw), validated by the
+ * caller.  Writes no maps. */
+int fcd_tile_confusion(const float* cmap, const float* ref_tiles, const int32_t* rects, int n, int ph, int pw, float thresh,
+                       float gt0, float gt1, float pre0, float pre1, unsigned long long* counts, void* stream);
+
 /* ---- loss terms ------------------------------------------------------------
  * Masked per-sample sums -- the reconstruction terms of Loss.py:76-84 (L1) and
  * :110-119 (MSE), and region_loss Loss.py:127-141:
