@@ -1619,6 +1619,20 @@ def tile_confusion(cmap, ref_tiles, rects, counts, prob_thresh=0.5, gt_map=(0, 1
     if cmap.dim() != 4 or cmap.shape[1] != 1 or cmap.shape != ref_tiles.shape:
         raise _lib.FcdError('tile_confusion: cmap and reference tiles must both be (N,1,ph,pw)')
     N, _, ph, pw = cmap.shape
+    if isinstance(rects, DeviceRects):          # resident rectangles through a resident index list: no upload here
+        if rects.table.patch != (pw, ph):
+            raise _lib.FcdError('tile_confusion: the rectangles were validated for patch %dx%d, the tiles are %dx%d'
+                                % (rects.table.patch + (pw, ph)))
+        if not 0 < rects.n <= N:
+            raise _lib.FcdError('tile_confusion: %d rectangles for %d tiles' % (rects.n, N))
+        counts = _counts_arg(counts, cmap.device)
+        if counts is None:
+            raise _lib.FcdError('tile_confusion: counts is required')
+        check(lib.fcd_tile_confusion_items(_p(cmap), _p(ref_tiles), _p(rects.table.to(cmap.device)[1]), len(rects.table),
+                                           _p(rects.index.on(cmap.device)), rects.n, ph, pw, float(prob_thresh), float(gt_map[0]),
+                                           float(gt_map[1]), float(pre_map[0]), float(pre_map[1]), _p(counts), _stream()),
+              'fcd_tile_confusion_items')
+        return counts
     rc = np.asarray(rects, dtype=np.int64).reshape(-1, 4)
     if not 0 < rc.shape[0] <= N:
         raise _lib.FcdError('tile_confusion: %d rectangles for %d tiles' % (rc.shape[0], N))
@@ -1632,6 +1646,223 @@ def tile_confusion(cmap, ref_tiles, rects, counts, prob_thresh=0.5, gt_map=(0, 1
                                  float(gt_map[1]), float(pre_map[0]), float(pre_map[1]), _p(counts), _stream()),
           'fcd_tile_confusion')
     return counts
+
+
+# ------------------------------------------------------- device-resident training feed (csrc/scene.hip)
+def _exact_meanstd(n, s1, s2):
+    """fp64 (mean, std) of n integer samples with sum s1 and sum of squares s2 (Python integers): the exact rationals
+    s1 / n and (n s2 - s1^2) / (n (n - 1)), each rounded once (std: once more by the square root)."""
+    import fractions
+    import math
+    mean = fractions.Fraction(s1, n)
+    var = fractions.Fraction(n * s2 - s1 * s1, n * (n - 1))
+    return float(mean), math.sqrt(float(var))
+
+
+@torch.no_grad()
+def scene_stats(scene_x, scene_y, table, sample_type=None, out=None):
+    """``(meanX, stdX, meanY, stdY, n)``: the masked per-band statistics of a resident scene pair ``(C,H,W)`` over the read
+    rectangles of ``table`` (CommonFunc.Dataset_mean / Dataset_std: valid = band sum of scene x non-zero, a pixel read by two
+    tiles counts twice; std over n - 1) as float64 arrays and the valid count.  uint8 / uint16: exact 64-bit integer moments
+    from the device, turned into fp64 by exact rational arithmetic here.  float32: two fp64 passes on the device, reproducible
+    bit for bit.  ``out``: the device buffer of 1 + 4*C raw totals (int64 for integer scenes, float64 for float32) to reuse."""
+    import numpy as np
+    sx, st = _scene_tensor(scene_x, 'scene_x', sample_type)
+    sy, st_y = _scene_tensor(scene_y, 'scene_y', sample_type)
+    if sx.dim() != 3 or sx.shape != sy.shape or st != st_y:
+        raise _lib.FcdError('scene_stats: the two scenes must be (C,H,W) tensors of one shape and sample type')
+    C, H, W = sx.shape
+    table = _table_for(table, W, H)
+    _, _, pw, ph, _, _ = table.geom
+    n, dev = len(table), sx.device
+    integer = st != SAMPLE_F32
+    if integer:
+        vmax = 255 if st == SAMPLE_U8 else 65535
+        pixels = int((table.rows[:, 6].astype(np.int64) * table.rows[:, 7].astype(np.int64)).sum())
+        if pixels * vmax * vmax >= 2 ** 64:
+            raise _lib.FcdError('scene_stats: %d pixels of up to %d: the sum of squares may exceed 2^64' % (pixels, vmax))
+    want = torch.int64 if integer else torch.float64
+    if out is None:
+        out = torch.empty(1 + 4 * C, dtype=want, device=dev)
+    elif not out.is_cuda or out.device != dev or out.dtype != want or out.numel() != 1 + 4 * C or not out.is_contiguous():
+        raise _lib.FcdError('scene_stats: out must be a contiguous device %s tensor of 1 + 4*C elements' % want)
+    nbytes = lib.fcd_scene_stats_ws_bytes(st, C, n, ph)
+    ws = None if integer else _ws(nbytes, dev)
+    check(lib.fcd_scene_stats(_p(sx), _p(sy), st, C, H, W, _p(table.to(dev)), n, ph, pw, _p(out), _p(ws), nbytes, _stream()),
+          'fcd_scene_stats')
+    tot = out.cpu().numpy()
+    if integer:
+        tot = [int(v) & (2 ** 64 - 1) for v in tot.tolist()]          # the kernel's counters are unsigned
+        cnt = tot[0]
+        if cnt < 2:
+            raise _lib.FcdError('scene_stats: %d valid pixels; mean and std need two' % cnt)
+        mx, sx_, my, sy_ = (np.empty(C, np.float64) for _ in range(4))
+        for c in range(C):
+            mx[c], sx_[c] = _exact_meanstd(cnt, tot[1 + c], tot[1 + C + c])
+            my[c], sy_[c] = _exact_meanstd(cnt, tot[1 + 2 * C + c], tot[1 + 3 * C + c])
+        return mx, sx_, my, sy_, cnt
+    cnt = int(tot[0])
+    if cnt < 2:
+        raise _lib.FcdError('scene_stats: %d valid pixels; mean and std need two' % cnt)
+    return (tot[1:1 + C].copy(), np.sqrt(tot[1 + 2 * C:1 + 3 * C] / (cnt - 1)), tot[1 + C:1 + 2 * C].copy(),
+            np.sqrt(tot[1 + 3 * C:1 + 4 * C] / (cnt - 1)), cnt)
+
+
+def validate_set_rows(rows, sizes, pw, ph, padx, pady):
+    """Raise FcdError unless every (T,13) row of a scene SET's tile table -- the 12 columns + the scene index -- names one of the
+    ``sizes`` = [(W, H), ...] and passes :func:`validate_tile_rows` against THAT scene."""
+    import numpy as np
+    r = np.asarray(rows)
+    if r.ndim != 2 or r.shape[1] != 13 or r.shape[0] == 0:
+        raise _lib.FcdError('scene set table: expected (T,13) rows with T > 0, got shape %s' % (r.shape,))
+    r = r.astype(np.int64)
+    s = r[:, 12]
+    bad = (s < 0) | (s >= len(sizes))
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise _lib.FcdError('scene set table row %d: scene index %d with %d scenes' % (i, int(s[i]), len(sizes)))
+    for k, (W, H) in enumerate(sizes):
+        sel = r[s == k]
+        if sel.shape[0]:
+            try:
+                validate_tile_rows(sel[:, :12], W, H, pw, ph, padx, pady)
+            except _lib.FcdError as e:
+                raise _lib.FcdError('scene %d of the set: %s' % (k, e))
+
+
+class SceneSetTable:
+    """The validated tile table of a scene set: ``rows`` = host int32 (T,13), the 12 columns of :class:`TileTable` + the scene
+    index, over ALL tiles of the set in global item order; ``rects`` = host int32 (T,4), ``TileGrid.eff_range`` per tile;
+    ``sizes`` = [(W, H)] per scene.  Uploaded once per device (:meth:`to`)."""
+
+    def __init__(self, rows, rects, sizes, patch, pad):
+        import numpy as np
+        self.sizes, self.patch, self.pad = [(int(w), int(h)) for w, h in sizes], tuple(patch), tuple(pad)
+        validate_set_rows(rows, self.sizes, self.patch[0], self.patch[1], self.pad[0], self.pad[1])
+        rc = np.asarray(rects, dtype=np.int64).reshape(-1, 4)
+        pw, ph = self.patch
+        if rc.shape[0] != np.asarray(rows).shape[0] or (rc < 0).any() or (rc[:, 1] > ph).any() or (rc[:, 3] > pw).any() or \
+                (rc[:, 0] > rc[:, 1]).any() or (rc[:, 2] > rc[:, 3]).any():
+            raise _lib.FcdError('scene set table: one rectangle per tile, inside the (%d,%d) tile' % (ph, pw))
+        self.rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).astype(np.int32))
+        self.rects = np.ascontiguousarray(rc.astype(np.int32))
+        self._dev = {}
+
+    def __len__(self):
+        return self.rows.shape[0]
+
+    def to(self, device):
+        """(tile table, rectangle table) on ``device``."""
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise _lib.FcdError('fcd_gan_pytorch_amd: the tile table goes to a CUDA/ROCm device, not %s (no CPU fallback)' % device)
+        if device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        if device not in self._dev:
+            self._dev[device] = (torch.from_numpy(self.rows).to(device), torch.from_numpy(self.rects).to(device))
+        return self._dev[device]
+
+
+def scene_set_table(grids):
+    """The :class:`SceneSetTable` of the scenes tiled by ``grids`` (``tiles.TileGrid`` each, one patch size and padding)."""
+    import numpy as np
+    geoms = {(g.patch_size, g.pad) for g in grids}
+    if len(geoms) != 1:
+        raise _lib.FcdError('scene set: the scenes must share patch size and padding, got %s' % sorted(geoms))
+    rows, rects = [], []
+    for s, g in enumerate(grids):
+        for i in range(len(g)):
+            rows.append(sum((list(t) for t in g.slices(i)), []) + [s])
+            rects.append(g.eff_range(i))
+    (patch, pad), = geoms
+    return SceneSetTable(np.array(rows, dtype=np.int64).reshape(-1, 13), rects, [(g.xsize, g.ysize) for g in grids], patch, pad)
+
+
+class TileIndex:
+    """A list of rows of a resident table, validated on the host (every entry in [0, size)) and uploaded ONCE, from pinned
+    memory without making the host wait; ``index[a:b]`` is a view of the device copy -- a batch of an epoch's plan."""
+
+    def __init__(self, items, size, device=None, _view=None):
+        import numpy as np
+        if _view is not None:
+            self.size, self.dev = size, _view
+            return
+        a = np.asarray(items, dtype=np.int64).reshape(-1)
+        if a.size == 0 or (a < 0).any() or (a >= size).any():
+            raise _lib.FcdError('tile index: %d entries, all must lie in [0, %d)' % (a.size, size))
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise _lib.FcdError('fcd_gan_pytorch_amd: the tile index goes to a CUDA/ROCm device, not %s (no CPU fallback)' % device)
+        self.size = int(size)
+        self.dev = torch.from_numpy(a.astype(np.int32)).pin_memory().to(device, non_blocking=True)
+
+    def __len__(self):
+        return self.dev.shape[0]
+
+    def __getitem__(self, s):
+        if not isinstance(s, slice) or s.step not in (None, 1):
+            raise TypeError('TileIndex takes contiguous slices')
+        return TileIndex(None, self.size, _view=self.dev[s])
+
+    def on(self, device):
+        if self.dev.device != torch.device(device) and torch.device(device).index is not None:
+            raise _lib.FcdError('tile index lives on %s, the tiles on %s' % (self.dev.device, device))
+        return self.dev
+
+
+class DeviceRects:
+    """The metric's rectangles for the first ``n`` tiles of a batch cut through ``index`` from the set ``table``: resident, so
+    ``Evaluator.add_tiles`` / :func:`tile_confusion` upload nothing."""
+
+    def __init__(self, table, index, n=None):
+        if not isinstance(table, SceneSetTable) or not isinstance(index, TileIndex) or index.size != len(table):
+            raise _lib.FcdError('DeviceRects: a SceneSetTable and a TileIndex validated against it')
+        self.table, self.index = table, index
+        self.n = len(index) if n is None else int(n)
+        if not 0 <= self.n <= len(index):
+            raise _lib.FcdError('DeviceRects: n = %d with %d indices' % (self.n, len(index)))
+
+
+SCENE_DESC_COLS = 8      # fcd_scene_desc as int64 columns: x, y, ref, region, H, W, stats_off, ref_type | region_type << 32
+
+
+@torch.no_grad()
+def scene_set_cut(descs, table, index, C, sample_type, stats=None, want_ref=True, want_region=True, want_valid=True, out=None):
+    """Cut the tiles ``index`` (a :class:`TileIndex` into ``table``, a :class:`SceneSetTable`) out of the resident scenes that
+    ``descs`` describes -- device int64 (S, 8) rows of ``fcd_scene_desc``, built by ``tiles.ResidentSceneSet`` from the tensors it
+    keeps alive -- in one launch.  ``stats``: device float64 tensor the descriptors' statistics offsets point into, or None
+    for plain samples.  Returns ``(x, y, ref, region, valid)`` like :func:`scene_cut` (+ the region tiles of
+    ``RegionTileDataset``); ``out`` = such a tuple of preallocated contiguous tensors; every element is written."""
+    if not isinstance(table, SceneSetTable) or not isinstance(index, TileIndex) or index.size != len(table):
+        raise _lib.FcdError('scene_set_cut: pass a SceneSetTable and a TileIndex validated against it')
+    if not torch.is_tensor(descs) or not descs.is_cuda or descs.dtype != torch.int64 or descs.dim() != 2 or \
+            tuple(descs.shape) != (len(table.sizes), SCENE_DESC_COLS) or not descs.is_contiguous():
+        raise _lib.FcdError('scene_set_cut: descs must be a contiguous device int64 (%d, %d) tensor' % (len(table.sizes), SCENE_DESC_COLS))
+    if sample_type not in (SAMPLE_U8, SAMPLE_U16, SAMPLE_F32) or C <= 0:
+        raise _lib.FcdError('scene_set_cut: sample type %r, %r bands' % (sample_type, C))
+    dev, S = descs.device, len(table.sizes)
+    s = None
+    if stats is not None:
+        if not torch.is_tensor(stats) or not stats.is_cuda or stats.dtype != torch.float64 or stats.numel() != S * 4 * C:
+            raise _lib.FcdError('scene_set_cut: stats must be a device float64 tensor of S*4*C values')
+        s = stats.contiguous()
+    n, (pw, ph) = len(index), table.patch
+    shapes = ((n, C, ph, pw), (n, C, ph, pw), (n, 1, ph, pw), (n, 1, ph, pw), (n, 1, ph, pw))
+    if out is None:
+        wants = (True, True, want_ref, want_region, want_valid)
+        out = tuple(torch.empty(sh, dtype=torch.float32, device=dev) if w else None for sh, w in zip(shapes, wants))
+    else:
+        out = tuple(out)
+        if len(out) != 5 or out[0] is None or out[1] is None:
+            raise _lib.FcdError('scene_set_cut: out = (x, y, ref or None, region or None, valid or None)')
+        for t, shape, name in zip(out, shapes, ('x', 'y', 'ref tiles', 'region tiles', 'valid')):
+            if t is not None and (_dev(t, 'out ' + name) is not t or tuple(t.shape) != shape or t.device != dev):
+                raise _lib.FcdError('scene_set_cut: out %s must be a contiguous %s float32 tensor on %s' % (name, shape, dev))
+    x, y, rtile, region, valid = out
+    tab, _ = table.to(dev)
+    check(lib.fcd_scene_set_cut(_p(descs), S, sample_type, C, _p(tab), len(table), _p(index.on(dev)), n, ph, pw, _p(s), _p(x), _p(y),
+                                _p(rtile), _p(region), _p(valid), _stream()), 'fcd_scene_set_cut')
+    return out
 
 
 # ------------------------------------------------------------------------ losses

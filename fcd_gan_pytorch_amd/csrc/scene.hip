@@ -15,6 +15,8 @@
 // canvas rows in groups of one per wavefront, y = the planes (cut) or tiles (stitch, confusion) behind a grid-stride loop
 // capped at the y limit, so any n*planes fits; all offsets into the scene and the canvases are 64-bit.  Wave index, plane
 // and table row are wave-uniform (readfirstlane): the decode runs on the scalar unit and the table comes in by scalar loads.
+#include <type_traits>
+
 #include "common.h"
 
 enum { T_X0 = 0, T_Y0, T_W, T_H, T_RX, T_RY, T_RW, T_RH, T_WX, T_WY, T_WW, T_WH, T_COLS };
@@ -175,14 +177,18 @@ __global__ __launch_bounds__(kCountBlock) void fcd_scene_stitch_kernel(
 
 // ---- confusion counts over tiles (the training loops' metric) --------------------------------------------------------------
 // rects: int32 (n,4) = r0,r1,c0,c1 (TileGrid.eff_range); one wave per (tile, canvas row), rows outside [r0,r1) skipped.
+// With ``index`` (fcd_tile_confusion_items) tile t takes row index[t] of a resident table of T rectangles; an index outside the
+// table (the host validates the list before upload) counts nothing.
 __global__ __launch_bounds__(kCountBlock) void fcd_tile_confusion_kernel(
-    const float* __restrict__ cmap, const float* __restrict__ ref_tiles, const int32_t* __restrict__ rects, int n,
-    int ph, int pw, SceneCountArgs a, unsigned long long* __restrict__ counts) {
+    const float* __restrict__ cmap, const float* __restrict__ ref_tiles, const int32_t* __restrict__ rects,
+    const int32_t* __restrict__ index, int T, int n, int ph, int pw, SceneCountArgs a, unsigned long long* __restrict__ counts) {
   const int lane = threadIdx.x & (FCD_WAVE - 1);
   const int j = wave_row<kCountWaves>();
   unsigned long long cnt[4] = {0, 0, 0, 0};
   for (long long t = blockIdx.y; t < n; t += gridDim.y) {
-    const int32_t* __restrict__ rc = rects + t * 4;
+    const long long g = index ? (long long)index[t] : t;
+    if (index && (g < 0 || g >= T)) continue;                // wave-uniform
+    const int32_t* __restrict__ rc = rects + g * 4;
     const int r0 = rc[0], r1 = rc[1], c0 = rc[2], c1 = rc[3];
     if (j < r0 || j >= r1) continue;                         // wave-uniform (r1 <= ph)
     const long long base = (t * ph + j) * pw;
@@ -248,7 +254,269 @@ extern "C" int fcd_tile_confusion(const float* cmap, const float* ref_tiles, con
   FcdProfScope prof(FCD_K_MISC, (hipStream_t)stream, 0.0, (double)rows * pw * 8.0);
   const SceneCountArgs a{thresh, gt0, gt1, pre0, pre1};
   hipLaunchKernelGGL(fcd_tile_confusion_kernel, count_grid(ph, n), dim3(kCountBlock), 0, (hipStream_t)stream, cmap, ref_tiles,
-                     rects, n, ph, pw, a, counts);
+                     rects, (const int32_t*)nullptr, 0, n, ph, pw, a, counts);
   FCD_LAUNCH_CHECK("fcd_tile_confusion");
+  return FCD_OK;
+}
+
+extern "C" int fcd_tile_confusion_items(const float* cmap, const float* ref_tiles, const int32_t* rect_table, int T,
+                                        const int32_t* index, int n, int ph, int pw, float thresh, float gt0, float gt1,
+                                        float pre0, float pre1, unsigned long long* counts, void* stream) {
+  FCD_CHECK_ARG(cmap && ref_tiles && rect_table && index && counts && T > 0 && n > 0 && ph > 0 && pw > 0,
+                "fcd_tile_confusion_items: bad arguments");
+  const long long rows = (long long)n * ph;
+  FcdProfScope prof(FCD_K_MISC, (hipStream_t)stream, 0.0, (double)rows * pw * 8.0);
+  const SceneCountArgs a{thresh, gt0, gt1, pre0, pre1};
+  hipLaunchKernelGGL(fcd_tile_confusion_kernel, count_grid(ph, n), dim3(kCountBlock), 0, (hipStream_t)stream, cmap, ref_tiles,
+                     rect_table, index, T, n, ph, pw, a, counts);
+  FCD_LAUNCH_CHECK("fcd_tile_confusion_items");
+  return FCD_OK;
+}
+
+// ==== the training feed: cut from a SET of resident scenes, statistics of a resident scene ===============================
+// ---- set cut ---------------------------------------------------------------------------------------------------------
+// fcd_scene_cut for tiles drawn from several resident scenes of different (H,W) in one launch.  Three resident inputs: the scene
+// descriptors (addresses, sizes, statistics offset), the table of ALL tiles of the set (the 12 columns + the scene index,
+// validated per scene on the host before its one upload) and the batch = a list of rows of that table.  planes of one tile:
+// C of x, C of y, [ref], [region], [valid]; the decode (index -> row -> scene -> plane) is wave-uniform.  An index outside the
+// table or a scene outside the descriptors (neither passes the host's validation) yields a zero tile instead of a wild read.
+enum { TS_SCENE = T_COLS, TS_COLS = T_COLS + 1 };
+
+__global__ __launch_bounds__(kBlock) void fcd_scene_set_cut_kernel(
+    const fcd_scene_desc* __restrict__ descs, int S, int stype, int C, const int32_t* __restrict__ table, int T,
+    const int32_t* __restrict__ index, int units, int ph, int pw, const double* __restrict__ stats, float* __restrict__ x,
+    float* __restrict__ y, float* __restrict__ ref_tiles, float* __restrict__ region_tiles, float* __restrict__ valid) {
+  const int lane = threadIdx.x & (FCD_WAVE - 1);
+  const unsigned planes = 2 * C + (ref_tiles ? 1 : 0) + (region_tiles ? 1 : 0) + (valid ? 1 : 0);
+  const int j = wave_row<kWaves>();
+  if (j >= ph) return;
+  for (unsigned pl = blockIdx.y; pl < (unsigned)units; pl += gridDim.y) {      // units = n * planes <= INT_MAX (checked by the host)
+    const long long t = pl / planes;
+    const int q = (int)(pl - (unsigned)t * planes);
+    const int g = index[t];
+    const bool row_ok = g >= 0 && g < T;
+    const int32_t* __restrict__ row = table + (long long)(row_ok ? g : 0) * TS_COLS;
+    const int s = row[TS_SCENE];
+    const bool ok = row_ok && s >= 0 && s < S;
+    const fcd_scene_desc* __restrict__ d = descs + (ok ? s : 0);
+    const long long H = d->H, W = d->W;
+    const int rx = row[T_RX], ry = row[T_RY], wx = row[T_WX], wy = row[T_WY], ww = row[T_WW], wh = row[T_WH];
+    const bool in_rows = ok && j >= wy && j < wy + wh;
+    const void* src = nullptr;
+    float* dst;
+    int type = stype, c = 0, k = q - 2 * C;
+    bool norm = false, ones = false, region = false;
+    if (q < C) {
+      src = (const void*)d->x; c = q; dst = x + ((t * C + c) * ph + j) * pw; norm = stats != nullptr && d->stats_off >= 0;
+    } else if (q < 2 * C) {
+      src = (const void*)d->y; c = q - C; dst = y + ((t * C + c) * ph + j) * pw; norm = stats != nullptr && d->stats_off >= 0;
+    } else if (ref_tiles && k == 0) {
+      src = (const void*)d->ref; type = d->ref_type; dst = ref_tiles + (t * ph + j) * pw;
+    } else if (region_tiles && k == (ref_tiles ? 1 : 0)) {
+      src = (const void*)d->region; type = d->region_type; region = true; dst = region_tiles + (t * ph + j) * pw;
+    } else {
+      ones = true; dst = valid + (t * ph + j) * pw;
+    }
+    double mean = 0.0, stdv = 1.0;
+    if (norm) {          // this scene's meanX[C], stdX[C], meanY[C], stdY[C]
+      const double* __restrict__ st = stats + d->stats_off + (q < C ? 0 : 2 * C);
+      mean = st[c]; stdv = st[C + c];
+    }
+    const bool live_plane = in_rows && (ones || src != nullptr);        // an absent map (address 0) gives zero tiles
+    const long long sbase = ((long long)c * H + (ry + (j - wy))) * W + (rx - wx);
+    for (int i = lane; i < pw; i += FCD_WAVE) {
+      float v = 0.f;
+      if (live_plane && i >= wx && i < wx + ww) {
+        if (ones) {
+          v = 1.f;
+        } else {
+          v = load_sample(src, sbase + i, type);
+          if (norm) v = (float)(((double)v - mean) / stdv);
+          if (region && v > 125.f) v = 1.f;                  // data_utils.py:280
+        }
+      }
+      dst[i] = v;
+    }
+  }
+}
+
+extern "C" int fcd_scene_set_cut(const fcd_scene_desc* descs, int S, int sample_type, int C, const int32_t* table, int T,
+                                 const int32_t* index, int n, int ph, int pw, const double* stats, float* x, float* y,
+                                 float* ref_tiles, float* region_tiles, float* valid, void* stream) {
+  FCD_CHECK_ARG(descs && table && index && x && y && S > 0 && C > 0 && T > 0 && n > 0 && ph > 0 && pw > 0,
+                "fcd_scene_set_cut: bad arguments");
+  FCD_CHECK_ARG(sample_type_ok(sample_type), "fcd_scene_set_cut: sample type %d (0 uint8, 1 uint16, 2 float32)", sample_type);
+  const int planes = 2 * C + (ref_tiles ? 1 : 0) + (region_tiles ? 1 : 0) + (valid ? 1 : 0);
+  const long long units = (long long)n * planes;
+  FCD_CHECK_ARG(units <= INT32_MAX, "fcd_scene_set_cut: %d tiles x %d planes exceed 2^31 - 1", n, planes);
+  const long long rows = units * ph;
+  const double in_bytes = sample_type == FCD_SAMPLE_U8 ? 1.0 : sample_type == FCD_SAMPLE_U16 ? 2.0 : 4.0;
+  FcdProfScope prof(FCD_K_MISC, (hipStream_t)stream, 0.0, (double)rows * pw * 4.0 + 2.0 * n * C * ph * pw * in_bytes);
+  hipLaunchKernelGGL(fcd_scene_set_cut_kernel, row_grid(ph, units), dim3(kBlock), 0, (hipStream_t)stream, descs, S, sample_type,
+                     C, table, T, index, (int)units, ph, pw, stats, x, y, ref_tiles, region_tiles, valid);
+  FCD_LAUNCH_CHECK("fcd_scene_set_cut");
+  return FCD_OK;
+}
+
+// ---- statistics ------------------------------------------------------------------------------------------------------
+// Masked per-band moments over the read rectangles of a tile table (CommonFunc.Dataset_mean / Dataset_std,
+// CommonFunc.py:436-500): a pixel counts when the fp32 band sum of scene x is non-zero (NaN != 0: counts), for both scenes,
+// once per tile that reads it.  One wave per (tile, row of the read rectangle): the mask of up to 64 x 64 columns is kept as
+// one bit per chunk in a 64-bit register per lane, then every band is read once more under it.  Lane totals -> wave total
+// (shuffles) -> the wave's OWN slots in LDS (plain adds, no atomics, in the fixed order of the wave's tiles) -> workgroup
+// total, summed over the waves in index order.
+//   MODE 0, uint8 / uint16: n, sum x[C], sum x^2[C], sum y[C], sum y^2[C] as exact unsigned 64-bit integers at every level; the
+//           workgroup totals go to the caller's totals by integer atomics (order-independent, so run-to-run identical).
+//   MODE 1, float32 pass 1: n, sum x[C], sum y[C] in fp64, one partial row per workgroup in the workspace.
+//   MODE 2, float32 pass 2: sum (x - mean)^2[C], sum (y - mean)^2[C] about the fp64 means of pass 1, partials likewise.
+// The partial rows are folded in index order by fcd_scene_stats_fold_kernel: no floating-point atomics anywhere, and the grid
+// depends on (n, ph) only, so two runs agree bit for bit.
+constexpr int kStatBands = 32;                                         // 16 waves x (1 + 4 * 32) slots x 8 B = 16.1 KB of LDS
+constexpr int kStatSegment = FCD_WAVE * 64;                            // columns one mask register per lane covers
+
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+template <typename T> __device__ __forceinline__ T wave_total(T v);
+template <> __device__ __forceinline__ unsigned long long wave_total(unsigned long long v) { return wave_sum_u64(v); }
+template <> __device__ __forceinline__ double wave_total(double v) { return wave_sum_d(v); }
+
+template <int MODE>
+__global__ __launch_bounds__(kCountBlock) void fcd_scene_stats_kernel(
+    const void* __restrict__ sx, const void* __restrict__ sy, int stype, int C, long long H, long long W,
+    const int32_t* __restrict__ table, int n, const double* __restrict__ mean, void* __restrict__ out) {
+  typedef typename std::conditional<MODE == 0, unsigned long long, double>::type acc_t;
+  __shared__ acc_t part[kCountWaves][1 + 4 * kStatBands];
+  const int lane = threadIdx.x & (FCD_WAVE - 1);
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int j = wave_row<kCountWaves>();
+  const int slots = MODE == 0 ? 1 + 4 * C : MODE == 1 ? 1 + 2 * C : 2 * C;
+  for (int k = lane; k < slots; k += FCD_WAVE) part[w][k] = 0;
+  __syncthreads();
+  for (long long t = blockIdx.y; t < n; t += gridDim.y) {    // no early return: every wave reaches the barrier below
+    const int32_t* __restrict__ row = table + t * T_COLS;
+    const int rx = row[T_RX], ry = row[T_RY], rw = row[T_RW], rh = row[T_RH];
+    if (j >= rh) continue;                                    // wave-uniform
+    const long long rbase = (long long)(ry + j) * W + rx;    // first sample of this row in band 0
+    for (int seg = 0; seg < rw; seg += kStatSegment) {
+      const int chunks = std::min(64, (rw - seg + FCD_WAVE - 1) / FCD_WAVE);
+      unsigned long long bits = 0;                           // bit k: column seg + 64 k + lane is valid
+      for (int k = 0; k < chunks; ++k) {
+        const int i = seg + k * FCD_WAVE + lane;
+        if (i < rw) {
+          float s = 0.f;
+          for (int c = 0; c < C; ++c) s += load_sample(sx, (long long)c * H * W + rbase + i, stype);
+          if (s != 0.f) bits |= 1ull << k;
+        }
+      }
+      if (MODE != 2) {
+        const acc_t cnt = wave_total<acc_t>((acc_t)__popcll(bits));
+        if (lane == 0) part[w][0] += cnt;
+      }
+      for (int c = 0; c < C; ++c) {
+        acc_t a0 = 0, a1 = 0, b0 = 0, b1 = 0;
+        const long long cbase = (long long)c * H * W + rbase;
+        for (int k = 0; k < chunks; ++k) {
+          if (!((bits >> k) & 1)) continue;
+          const int i = seg + k * FCD_WAVE + lane;
+          const float vx = load_sample(sx, cbase + i, stype), vy = load_sample(sy, cbase + i, stype);
+          if (MODE == 0) {                                   // uint8 / uint16 samples: exact in float, exact back
+            const acc_t ux = (acc_t)(unsigned)vx, uy = (acc_t)(unsigned)vy;
+            a0 += ux; a1 += ux * ux; b0 += uy; b1 += uy * uy;
+          } else if (MODE == 1) {
+            a0 += (acc_t)vx; b0 += (acc_t)vy;
+          } else {
+            const double dx = (double)vx - mean[c], dy = (double)vy - mean[C + c];
+            a0 += (acc_t)(dx * dx); b0 += (acc_t)(dy * dy);
+          }
+        }
+        a0 = wave_total<acc_t>(a0); b0 = wave_total<acc_t>(b0);
+        if (MODE == 0) { a1 = wave_total<acc_t>(a1); b1 = wave_total<acc_t>(b1); }
+        if (lane == 0) {
+          if (MODE == 0) {
+            part[w][1 + c] += a0; part[w][1 + C + c] += a1; part[w][1 + 2 * C + c] += b0; part[w][1 + 3 * C + c] += b1;
+          } else if (MODE == 1) {
+            part[w][1 + c] += a0; part[w][1 + C + c] += b0;
+          } else {
+            part[w][c] += a0; part[w][C + c] += b0;
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < slots) {
+    acc_t s = 0;
+    for (int k = 0; k < kCountWaves; ++k) s += part[k][threadIdx.x];
+    if (MODE == 0) {
+      if (s) atomicAdd((unsigned long long*)out + threadIdx.x, (unsigned long long)s);
+    } else {
+      ((double*)out)[((long long)blockIdx.y * gridDim.x + blockIdx.x) * slots + threadIdx.x] = (double)s;
+    }
+  }
+}
+
+// out[k] = sum over the workgroups' partial rows, in index order; with ``means`` slot 0 is the count n and every other slot is
+// divided by it.
+__global__ __launch_bounds__(kBlock) void fcd_scene_stats_fold_kernel(const double* __restrict__ partials, int blocks, int slots,
+                                                                     int means, double* __restrict__ out) {
+  const int k = threadIdx.x;
+  if (k >= slots) return;
+  double s = 0.0, cnt = 0.0;
+  for (int b = 0; b < blocks; ++b) {
+    s += partials[(long long)b * slots + k];
+    if (means) cnt += partials[(long long)b * slots];
+  }
+  out[k] = means && k > 0 ? s / cnt : s;
+}
+
+static inline int stats_blocks(int n, int ph) {
+  const dim3 g = count_grid(ph, n);
+  return (int)(g.x * g.y);
+}
+
+extern "C" size_t fcd_scene_stats_ws_bytes(int sample_type, int C, int n, int ph) {
+  if (sample_type != FCD_SAMPLE_F32 || C <= 0 || C > kStatBands || n <= 0 || ph <= 0) return 0;
+  return (size_t)stats_blocks(n, ph) * (1 + 2 * C) * sizeof(double);
+}
+
+extern "C" int fcd_scene_stats(const void* scene_x, const void* scene_y, int sample_type, int C, int H, int W,
+                               const int32_t* table, int n, int ph, int pw, void* out, void* ws, size_t ws_bytes, void* stream) {
+  FCD_CHECK_ARG(scene_x && scene_y && table && out && C > 0 && H > 0 && W > 0 && n > 0 && ph > 0 && pw > 0,
+                "fcd_scene_stats: bad arguments");
+  FCD_CHECK_ARG(sample_type_ok(sample_type), "fcd_scene_stats: sample type %d (0 uint8, 1 uint16, 2 float32)", sample_type);
+  FCD_CHECK_ARG(C <= kStatBands, "fcd_scene_stats: %d bands, at most %d", C, kStatBands);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid = count_grid(ph, n);
+  const double bytes = (double)n * ph * pw * (3.0 * C) * (sample_type == FCD_SAMPLE_U8 ? 1.0 : sample_type == FCD_SAMPLE_U16 ? 2.0 : 4.0);
+  if (sample_type != FCD_SAMPLE_F32) {
+    const unsigned long long vmax = sample_type == FCD_SAMPLE_U8 ? 255ull : 65535ull;
+    const unsigned long long pixels = (unsigned long long)n * (unsigned long long)ph * (unsigned long long)pw;
+    FCD_CHECK_ARG(pixels < UINT64_MAX / (vmax * vmax), "fcd_scene_stats: %d tiles of %dx%d: the sum of squares may exceed 2^64", n,
+                  pw, ph);
+    FcdProfScope prof(FCD_K_MISC, st, 0.0, bytes);
+    if (hipMemsetAsync(out, 0, (size_t)(1 + 4 * C) * sizeof(unsigned long long), st) != hipSuccess) {
+      fcd_set_error("fcd_scene_stats: clearing the totals failed");
+      return FCD_ERR_LAUNCH;
+    }
+    hipLaunchKernelGGL(fcd_scene_stats_kernel<0>, grid, dim3(kCountBlock), 0, st, scene_x, scene_y, sample_type, C, (long long)H,
+                       (long long)W, table, n, (const double*)nullptr, out);
+    FCD_LAUNCH_CHECK("fcd_scene_stats");
+    return FCD_OK;
+  }
+  const size_t need = fcd_scene_stats_ws_bytes(sample_type, C, n, ph);
+  FCD_CHECK_ARG(ws && ws_bytes >= need, "fcd_scene_stats: workspace of %zu bytes, %zu needed", ws_bytes, need);
+  FcdProfScope prof(FCD_K_MISC, st, 0.0, 2.0 * bytes);
+  const int blocks = (int)(grid.x * grid.y);
+  double* o = (double*)out;                                  // n | meanX[C] meanY[C] | ssX[C] ssY[C]
+  hipLaunchKernelGGL(fcd_scene_stats_kernel<1>, grid, dim3(kCountBlock), 0, st, scene_x, scene_y, sample_type, C, (long long)H,
+                     (long long)W, table, n, (const double*)nullptr, ws);
+  hipLaunchKernelGGL(fcd_scene_stats_fold_kernel, dim3(1), dim3(kBlock), 0, st, (const double*)ws, blocks, 1 + 2 * C, 1, o);
+  hipLaunchKernelGGL(fcd_scene_stats_kernel<2>, grid, dim3(kCountBlock), 0, st, scene_x, scene_y, sample_type, C, (long long)H,
+                     (long long)W, table, n, (const double*)(o + 1), ws);
+  hipLaunchKernelGGL(fcd_scene_stats_fold_kernel, dim3(1), dim3(kBlock), 0, st, (const double*)ws, blocks, 2 * C, 0, o + 1 + 2 * C);
+  FCD_LAUNCH_CHECK("fcd_scene_stats");
   return FCD_OK;
 }

@@ -76,12 +76,18 @@ def demo_usss(scene_x, scene_y, ref=None, device='cuda', patch_size=(220, 220), 
               epochs_g=50, epochs_s=50, epochs_joint=100, batch_size=10, learning_rate=2e-4,
               perception_weight=0.4, l1_weight=0.65, ssim_weight=0, perception_perBand=True,
               prob_thresh=0.5, gt_map=(1, 2), pre_map=(0, 1), seed=0, out_density=None, out_color=None,
-              log=None, allow_seeded=False, stats_txt=None, save_s=None, save_g=None, ragged='pad', resident_inference=False):
+              log=None, allow_seeded=False, stats_txt=None, save_s=None, save_g=None, ragged='pad', resident_inference=False,
+              resident_training=False):
     """Demo_USSS.py:29-501: G pre-train -> S pre-train -> joint training -> inference with centre write-back, with the
     reference's LR schedules (Demo_USSS.py:133,201,298-299) and per-tile dataset statistics (:88-95).
     ``scene_x/scene_y/ref``: (bands,H,W) arrays or TIFF paths; ``save_s`` / ``save_g``: ``.pkl`` paths
     (Demo_USSS.py:477-481).  ``batch_size`` is per rank under data parallelism.  ``resident_inference=True`` runs the final
     inference with the scene pair and the maps resident on the device (``infer_scene_resident``: same maps and scores).
+    ``resident_training=True`` uploads ONE ``tiles.ResidentScene`` that serves the statistics (``scene.statistics`` /
+    ``tiles.scene_meanstd`` when ``stats_txt`` is given: exact moments, equal to the host's to about seven digits), all three
+    training phases (``ResidentSceneSet.epoch``: same batches, tiles bit-identical for the same statistics), the joint phase's
+    accuracy (counted over each tile's owned centre, ``Evaluator.add_tiles`` on resident rectangles -- with overlapped tiles
+    the host route counts the context ring too) and the final inference.
     Returns dict(netS, netG, density (1,H,W) float32, color (1,H,W), evaluator, history, vgg_pretrained)."""
     dev = torch.device(device)
     if isinstance(scene_x, str):
@@ -90,7 +96,17 @@ def demo_usss(scene_x, scene_y, ref=None, device='cuda', patch_size=(220, 220), 
         scene_y = tiles.read_tiff(scene_y)
     if isinstance(ref, str):
         ref = tiles.read_tiff(ref)
-    stats = _tile_stats(scene_x, scene_y, patch_size, stats_txt)
+    scene = None
+    if resident_training:
+        scene = tiles.ResidentScene(scene_x, scene_y, ref, patch_size, overlap_padding, device=dev)
+        stats = tiles.scene_meanstd(stats_txt[0], stats_txt[1], scene) if stats_txt else scene.statistics()
+        stats = tuple(np.asarray(v, np.float64) for v in stats)
+        scene.set_stats(stats)
+        feed = tiles.ResidentSceneSet([scene])
+        epoch = lambda sd: feed.epoch(batch_size, sd, ragged=ragged)
+    else:
+        stats = _tile_stats(scene_x, scene_y, patch_size, stats_txt)
+        epoch = lambda sd: _Epoch(ds, batch_size, sd, dev, ragged=ragged)
     ds = tiles.PairTileDataset(scene_x, scene_y, ref, patch_size, overlap_padding, stats=stats)
     nband = scene_x.shape[0]
     torch.manual_seed(seed)
@@ -109,7 +125,7 @@ def demo_usss(scene_x, scene_y, ref=None, device='cuda', patch_size=(220, 220), 
     for ep in range(epochs_g):                                                   # Demo_USSS.py:126-189
         optim.adjust_learning_rate(optG, ep, lr_start=1e-5, lr_max=3e-4, lr_warm_up_epoch=10, lr_sustain_epochs=10)
         tot = torch.zeros((), device=dev)
-        for (x, y, item, r), real, w in _Epoch(ds, batch_size, seed * 1000 + ep, dev, ragged=ragged):
+        for (x, y, item, r), real, w in epoch(seed * 1000 + ep):
             out = steps.usss_g_pretrain_step(netG, crit, optG, x, y, **kw, loss_scale=w.loss_scale)
             tot += out['loss'].detach() * w
         hist['g'].append(float(_epoch_mean(tot)))
@@ -118,7 +134,7 @@ def demo_usss(scene_x, scene_y, ref=None, device='cuda', patch_size=(220, 220), 
     for ep in range(epochs_s):                                                   # Demo_USSS.py:194-286
         optim.adjust_learning_rate(optS, ep, lr_start=1e-5, lr_max=3e-4, lr_warm_up_epoch=10, lr_sustain_epochs=10)
         tot = torch.zeros((), device=dev)
-        for (x, y, item, r), real, w in _Epoch(ds, batch_size, seed * 1000 + 1000 + ep, dev, ragged=ragged):
+        for (x, y, item, r), real, w in epoch(seed * 1000 + 1000 + ep):
             out = steps.usss_s_pretrain_step(netS, netG, crit, optS, x, y, l1_weight=l1_weight, **kw, loss_scale=w.loss_scale)
             tot += out['net_loss'].detach() * w
         hist['s'].append(float(_epoch_mean(tot)))
@@ -129,10 +145,13 @@ def demo_usss(scene_x, scene_y, ref=None, device='cuda', patch_size=(220, 220), 
         optim.adjust_learning_rate(optG, ep, lr_start=1e-5, lr_max=1e-4)
         tot = torch.zeros((), device=dev)
         acc.reset()
-        for (x, y, item, r), real, w in _Epoch(ds, batch_size, seed * 1000 + 2000 + ep, dev, ragged=ragged):
+        for (x, y, item, r), real, w in epoch(seed * 1000 + 2000 + ep):
             out = steps.usss_joint_step(netS, netG, crit, optS, optG, x, y, l1_weight=l1_weight, **kw, loss_scale=w.loss_scale)
             tot += out['net_loss'].detach() * w
-            if ref is not None:
+            if ref is not None and resident_training:
+                if w.rects is not None:
+                    acc.add_tiles(r, out['cmap'].detach(), w.rects, prob_thresh, gt_map, pre_map)
+            elif ref is not None:
                 acc.add_batch_map(r, metrics.threshold_map(out['cmap'].detach(), prob_thresh), gt_map, pre_map,
                                   valid=_real_mask(r, real).expand_as(r))
         hist['joint'].append(float(_epoch_mean(tot)))
@@ -141,7 +160,8 @@ def demo_usss(scene_x, scene_y, ref=None, device='cuda', patch_size=(220, 220), 
 
     dp.sync_buffers((netS, netG))            # one set of BatchNorm statistics for the stitched map AND the checkpoint
     if resident_inference:
-        scene = tiles.ResidentScene(scene_x, scene_y, ref, patch_size, overlap_padding, stats=stats, device=dev)
+        if scene is None:
+            scene = tiles.ResidentScene(scene_x, scene_y, ref, patch_size, overlap_padding, stats=stats, device=dev)
         res = infer_scene_resident(netS, scene, dev, batch_size=batch_size, prob_thresh=prob_thresh, gt_map=gt_map,
                                    pre_map=pre_map)
     else:
@@ -263,8 +283,18 @@ def demo_rsss(dataset, device='cuda', n_channels=4, epochs_g=50, epochs_adv=100,
     generator checkpoint is given -- ``load_g``: path of a ``GModel.pkl`` as the reference writes it,
     Demo_RSSS.py:167-171, or ``netG_state``: a state_dict), netG.eval(), adversarial D/S loop with the
     reference's LR schedules, per-epoch on-device accuracy over the owned tile centres, ``.pkl`` checkpoints
-    (``save_s/save_g/save_d``, Demo_RSSS.py:507-514).  Batch sizes are per rank under data parallelism."""
+    (``save_s/save_g/save_d``, Demo_RSSS.py:507-514).  Batch sizes are per rank under data parallelism.
+    ``dataset`` may be a ``tiles.ResidentSceneSet`` (scenes with region maps, resident on the device): the same batches are
+    then cut on the device (``ResidentSceneSet.epoch``) and the accuracy is one ``Evaluator.add_tiles`` call per batch on
+    resident rectangles -- no host work per tile, no copy per batch."""
     dev = torch.device(device)
+    resident = isinstance(dataset, tiles.ResidentSceneSet)
+    if resident:
+        if not dataset.has_region:
+            raise ValueError('demo_rsss needs region maps: ResidentScene(..., region=...)')
+        epoch = lambda bs, sd: dataset.epoch(bs, sd, ragged=ragged)
+    else:
+        epoch = lambda bs, sd: _Epoch(dataset, bs, sd, dev, ragged=ragged)
     torch.manual_seed(seed)
     netD = Module.Discriminator_SRGAN_simple(n_channels=n_channels).to(dev)
     netS = Module.Segmentor(n_channels=n_channels, bilinear=True).to(dev)
@@ -285,7 +315,7 @@ def demo_rsss(dataset, device='cuda', n_channels=4, epochs_g=50, epochs_adv=100,
     for ep in range(epochs_g):                                                   # Demo_RSSS.py:175-236
         optim.adjust_learning_rate(optG, ep, lr_start=1e-5, lr_max=3e-4, lr_warm_up_epoch=10, lr_sustain_epochs=10)
         tot = torch.zeros((), device=dev)
-        for (x, y, item, r, region), real, w in _Epoch(dataset, init_batch_size, seed * 1000 + ep, dev, ragged=ragged):
+        for (x, y, item, r, region), real, w in epoch(init_batch_size, seed * 1000 + ep):
             out = steps.rsss_g_pretrain_step(netG, crit, optG, x, y, region, perception_weight, ssim_weight, loss_scale=w.loss_scale)
             tot += out['g_loss'].detach() * w
         hist['g'].append(float(_epoch_mean(tot)))
@@ -298,12 +328,16 @@ def demo_rsss(dataset, device='cuda', n_channels=4, epochs_g=50, epochs_adv=100,
         optim.adjust_learning_rate(optD, ep, lr_start=5e-6, lr_max=5e-5, lr_min=5e-7, lr_warm_up_epoch=5)
         acc.reset()
         sums = torch.zeros(3, device=dev)
-        for (x, y, item, r, region), real, w in _Epoch(dataset, batch_size, seed * 1000 + 500 + ep, dev, ragged=ragged):
+        for (x, y, item, r, region), real, w in epoch(batch_size, seed * 1000 + 500 + ep):
             out = steps.rsss_adversarial_step(netS, netD, netG, crit, optS, optD, x, y, region,
                                               perception_weight=perception_weight, ssim_weight=ssim_weight,
                                               l1_weight=l1_weight, g_weight=g_weight, d_weight=d_weight,
                                               r_weight=r_weight, loss_scale=w.loss_scale)
             sums += torch.stack([out['d_loss'].detach(), out['s_loss'].detach(), out['g_loss'].detach()]) * w
+            if resident:
+                if w.rects is not None:
+                    acc.add_tiles(r, out['cmap'].detach(), w.rects, prob_thresh, gt_map, pre_map)
+                continue
             valid = _valid_centres(dataset, out['cmap'], item.tolist(), real)
             acc.add_batch_map(r, metrics.threshold_map(out['cmap'].detach(), prob_thresh), gt_map, pre_map, valid=valid)
         hist['adv'].append([float(v) for v in _epoch_mean(sums)] + [float(acc.Pixel_F1_score())])

@@ -76,7 +76,8 @@ class Evaluator:
     def add_tiles(self, ref_tiles, cmap, rects, prob_thresh=0.5, gt_map=(0, 1), pre_map=(0, 1)):
         """``add_batch_map(ref_tiles, cmap > prob_thresh, gt_map, pre_map, valid=<rects>)`` as ONE kernel: the density tiles
         ``cmap`` (N,1,H,W) are thresholded, compared with the reference tiles and counted over ``rects`` = (r0, r1, c0, c1) per
-        tile (``TileGrid.eff_range``; fewer rects than tiles: the trailing padded duplicates are left out)."""
+        tile (``TileGrid.eff_range``; fewer rects than tiles: the trailing padded duplicates are left out) -- a host sequence,
+        uploaded here, or the resident ``_ops.DeviceRects`` of a ``tiles.ResidentSceneSet`` batch (no copy at all)."""
         from . import _ops as ops
         assert len(gt_map) == len(pre_map) == self.num_class
         ops.tile_confusion(cmap, ref_tiles, rects, self.device_counts(cmap.device), prob_thresh, gt_map, pre_map)

@@ -306,9 +306,13 @@ class ResidentScene:
     """A bi-temporal scene pair (+ optional reference map) that lives in device memory for a whole inference pass: uploaded
     ONCE in its own sample type (uint8 / uint16 / float32 -- a uint16 scene is half the bytes of its fp32 tiles), cut into
     the tiles of ``PairTileDataset`` on the device (``_ops.scene_cut``: same values bit for bit, no host loop, no pinned
-    staging).  The reference map goes up as float32, the form the stitch kernel compares in.  Single scene only."""
+    staging).  The reference map goes up as float32, the form the stitch kernel compares in; the optional weak ``region`` mask
+    (GDALDataset_RSS, data_utils.py:239-290) stays in its own sample type.  One scene; several of them make a
+    ``ResidentSceneSet``, the training feed.  ``stats='auto'``: the scene's own statistics (:meth:`statistics`), taken on the
+    device before anything is cut."""
 
-    def __init__(self, scene_x, scene_y, ref=None, patch_size=(200, 200), overlap_padding=(10, 10), stats=None, device='cuda'):
+    def __init__(self, scene_x, scene_y, ref=None, patch_size=(200, 200), overlap_padding=(10, 10), stats=None, device='cuda',
+                 region=None):
         from . import _ops as ops
         if isinstance(scene_x, str):
             scene_x = read_tiff(scene_x)
@@ -316,6 +320,8 @@ class ResidentScene:
             scene_y = read_tiff(scene_y)
         if isinstance(ref, str):
             ref = read_tiff(ref)
+        if isinstance(region, str):
+            region = read_tiff(region)
         scene_x, scene_y = np.asarray(scene_x), np.asarray(scene_y)
         if scene_x.shape != scene_y.shape or scene_x.ndim != 3:
             raise ValueError("Image sizes don't match")
@@ -324,25 +330,85 @@ class ResidentScene:
                                     % (scene_x.dtype, scene_y.dtype))
         if ref is not None and (ref.shape[0] != 1 or ref.shape[1:] != scene_x.shape[1:]):
             raise ValueError("Reference sizes don't match image")
+        if region is not None:
+            region = np.asarray(region)
+            if region.shape[0] != 1 or region.shape[1:] != scene_x.shape[1:]:
+                raise ValueError("Reference sizes don't match image")
+            if region.dtype not in (np.uint8, np.uint16, np.float32):
+                raise ops._lib.FcdError('ResidentScene: the region map must be uint8, uint16 or float32, got %s' % region.dtype)
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise ops._lib.FcdError('ResidentScene lives on a CUDA/ROCm device, not %s (no CPU fallback)' % self.device)
-        self.sample_type = {1: ops.SAMPLE_U8, 2: ops.SAMPLE_U16, 4: ops.SAMPLE_F32}[scene_x.dtype.itemsize]
+        sample_type = {1: ops.SAMPLE_U8, 2: ops.SAMPLE_U16, 4: ops.SAMPLE_F32}[scene_x.dtype.itemsize]
 
         def up(a):          # uint16 samples travel as int16 bits (same bytes; the kernel reads them as uint16)
             a = np.ascontiguousarray(a)
             return torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(self.device)
-        self.x, self.y = up(scene_x), up(scene_y)
-        self.ref = None if ref is None else torch.from_numpy(np.ascontiguousarray(ref, dtype=np.float32)).to(self.device)
-        self.grid = TileGrid(scene_x.shape[2], scene_x.shape[1], patch_size, overlap_padding)
-        self.bands = scene_x.shape[0]
-        self.stats = stats            # (meanX, stdX, meanY, stdY) per band, NORMALIZE semantics (as PairTileDataset)
-        self._stats_dev = None
+        self._attach(up(scene_x), up(scene_y), sample_type,
+                     None if ref is None else torch.from_numpy(np.ascontiguousarray(ref, dtype=np.float32)).to(self.device),
+                     ops.SAMPLE_F32, None if region is None else up(region),
+                     0 if region is None else {1: ops.SAMPLE_U8, 2: ops.SAMPLE_U16, 4: ops.SAMPLE_F32}[region.dtype.itemsize],
+                     patch_size, overlap_padding, stats)
+
+    @classmethod
+    def from_device(cls, x, y, ref=None, region=None, patch_size=(200, 200), overlap_padding=(10, 10), stats=None,
+                    sample_type=None, ref_type=None, region_type=None):
+        """A ResidentScene over tensors that already live on the device, copied nowhere: ``x``, ``y`` (C,H,W) of uint8, uint16 or
+        float32 samples (``sample_type=_ops.SAMPLE_U16`` for uint16 bits held in an int16 tensor), ``ref`` / ``region`` (1,H,W)
+        likewise (``ref_type`` / ``region_type``).  The stitch kernel of ``infer_scene_resident`` wants a float32 ``ref``."""
+        from . import _ops as ops
+        x, st = ops._scene_tensor(x, 'scene_x', sample_type)
+        y, st_y = ops._scene_tensor(y, 'scene_y', sample_type)
+        if x.dim() != 3 or x.shape != y.shape or st != st_y or x.device != y.device:
+            raise ops._lib.FcdError('ResidentScene: the two scenes must be (C,H,W) device tensors of one shape and sample type')
+        maps = []
+        for t, typ, name in ((ref, ref_type, 'reference map'), (region, region_type, 'region map')):
+            if t is None:
+                maps += [None, 0]
+                continue
+            t, typ = ops._scene_tensor(t, name, typ)
+            if t.numel() != x.shape[1] * x.shape[2] or t.device != x.device:
+                raise ValueError("Reference sizes don't match image")
+            maps += [t, typ]
+        self = cls.__new__(cls)
+        self.device = x.device
+        self._attach(x, y, st, maps[0], maps[1], maps[2], maps[3], patch_size, overlap_padding, stats)
+        return self
+
+    def _attach(self, x, y, sample_type, ref, ref_type, region, region_type, patch_size, overlap_padding, stats):
+        self.x, self.y, self.sample_type = x, y, sample_type
+        self.ref, self.ref_type, self.region, self.region_type = ref, ref_type, region, region_type
+        self.bands = int(x.shape[0])
+        self.grid = TileGrid(int(x.shape[2]), int(x.shape[1]), patch_size, overlap_padding)
+        self.stats, self._stats_dev, self.stats_count = None, None, None
+        if isinstance(stats, str):
+            if stats != 'auto':
+                raise ValueError("stats: (meanX, stdX, meanY, stdY), None or 'auto'")
+            stats = self.statistics()
+        self.set_stats(stats)
+
+    def set_stats(self, stats):
+        """``stats`` = (meanX, stdX, meanY, stdY) per band, NORMALIZE semantics (as PairTileDataset), or None."""
+        from . import _ops as ops
+        self.stats, self._stats_dev = stats, None
         if stats is not None:
             s = np.stack([np.asarray(v, dtype=np.float64).reshape(-1) for v in stats])
             if s.shape != (4, self.bands):
                 raise ops._lib.FcdError("ResidentScene: The input channel doesn't match the stats list")   # CommonFunc.py:212
             self._stats_dev = torch.from_numpy(np.ascontiguousarray(s)).to(self.device)
+
+    def statistics(self, overlap_padding=(0, 0)):
+        """``(meanX, stdX, meanY, stdY)`` as float64 arrays: CommonFunc.Dataset_mean / Dataset_std over the tiling of this scene
+        with its own patch size and ``overlap_padding`` -- what ``demos._tile_stats`` computes on the host, here in one pass
+        over the resident samples (``_ops.scene_stats``).  The values are the EXACT masked moments (integer scenes) or their
+        fp64 evaluation (float32); the host functions round every tile mean to fp32, so the two routes agree to about seven
+        digits.  Where the reference gives NaN (a tile without a valid pixel: mean of an empty selection times weight 0) this
+        gives the finite statistic of the remaining tiles.  ``stats_count`` keeps the number of valid pixels."""
+        from . import _ops as ops
+        grid = TileGrid(self.grid.xsize, self.grid.ysize, self.grid.patch_size, overlap_padding)
+        mx, sx, my, sy, self.stats_count = ops.scene_stats(self.x, self.y, ops.scene_tile_table(grid, range(len(grid))),
+                                                           sample_type=self.sample_type)
+        return mx, sx, my, sy
 
     def __len__(self):
         return len(self.grid)
@@ -358,13 +424,164 @@ class ResidentScene:
         ``valid`` window mask are (n,1,py,px)."""
         from . import _ops as ops
         return ops.scene_cut(self.x, self.y, self.table(items), ref=self.ref, stats=None if raw else self._stats_dev,
-                             sample_type=self.sample_type)
+                             sample_type=self.sample_type, ref_type=self.ref_type if self.ref is not None else None)
 
     def new_maps(self):
         """Zeroed ``density`` and ``color`` maps, (1,H,W) float32 on the device."""
         shape = (1, self.grid.ysize, self.grid.xsize)
         return (torch.zeros(shape, dtype=torch.float32, device=self.device),
                 torch.zeros(shape, dtype=torch.float32, device=self.device))
+
+
+class EpochWeight(float):
+    """A batch's epoch weight ``n_real / len(dataset)`` (a float) that also carries the step's ``loss_scale`` (``dp`` ragged=
+    'weighted') and, on the resident feed, ``rects``: the metric's rectangles of the batch's real tiles, on the device
+    (``Evaluator.add_tiles``); None when the batch holds no real tile."""
+    loss_scale = 1.0
+    rects = None
+
+
+class EpochPlan:
+    """What one rank does in one epoch, known before its first batch: ``batches`` (lists of global items), ``pads`` (trailing
+    padded duplicates per batch), ``scales`` (loss scale per batch) -- ``dp.RankStridedBatches``'s, same seed, same order --
+    and ``flat`` / ``offsets``: all batches laid end to end, batch b = ``flat[offsets[b]:offsets[b + 1]]``.  Pure host code."""
+
+    def __init__(self, n, batch_size, seed, shuffle=True, ragged='pad', rank=None, world=None):
+        from . import dp
+        sampler = dp.RankStridedBatches(n, batch_size, seed=seed, shuffle=shuffle, rank=rank, world=world, ragged=ragged)
+        self.batches = [list(b) for b in sampler]
+        self.pads, self.scales, self.n = list(sampler.pads), list(sampler.scales), int(n)
+        self.flat = [i for b in self.batches for i in b]
+        self.offsets = [0]
+        for b in self.batches:
+            self.offsets.append(self.offsets[-1] + len(b))
+
+    def __len__(self):
+        return len(self.batches)
+
+
+def check_scene_set(scenes):
+    """Raise FcdError unless the scenes of a set share band count, sample type, patch size, padding and device (host check;
+    reads ``bands``, ``sample_type``, ``grid.patch_size``, ``grid.pad`` and ``device`` only)."""
+    from . import _ops as ops
+    scenes = list(scenes)
+    if not scenes:
+        raise ops._lib.FcdError('ResidentSceneSet: no scene')
+    for what, get in (('band count', lambda s: s.bands), ('sample type', lambda s: s.sample_type),
+                      ('patch size', lambda s: tuple(s.grid.patch_size)), ('overlap padding', lambda s: tuple(s.grid.pad)),
+                      ('device', lambda s: s.device)):
+        got = [get(s) for s in scenes]
+        if any(g != got[0] for g in got):
+            raise ops._lib.FcdError('ResidentSceneSet: the scenes must share one %s, got %s' % (what, got))
+
+
+class ResidentSceneSet:
+    """Several ``ResidentScene`` of different sizes as ONE training set -- ``datasets.MultiSceneDataset`` over
+    ``RegionTileDataset`` with everything on the device.  Copies nothing: a descriptor table holds the scenes' addresses
+    (the set keeps the scenes alive), the table of all tiles goes up once, and a batch is a list of global items cut in one
+    launch (``_ops.scene_set_cut``) with each tile normalised by its own scene's statistics.  The scenes share band count,
+    sample type, patch size and padding.  Statistics are read when the set is made: call :meth:`refresh` after
+    ``ResidentScene.set_stats``."""
+
+    def __init__(self, scenes, names=None):
+        from . import _ops as ops
+        self.scenes = list(scenes)
+        check_scene_set(self.scenes)
+        self.names = list(names) if names is not None else ['scene%d' % i for i in range(len(self.scenes))]
+        self.numlist = [len(s) for s in self.scenes]
+        self.cumlen = np.cumsum(np.array(self.numlist)).tolist()
+        first = self.scenes[0]
+        self.device, self.bands, self.sample_type = first.x.device, first.bands, first.sample_type
+        self.patch_size, self.pad = first.grid.patch_size, first.grid.pad
+        self.table = ops.scene_set_table([s.grid for s in self.scenes])
+        self.has_ref = any(s.ref is not None for s in self.scenes)
+        self.has_region = any(s.region is not None for s in self.scenes)
+        self.refresh()
+
+    def refresh(self):
+        """Rebuild the descriptor table and the statistics array from the scenes' current tensors and statistics."""
+        C = self.bands
+        rows, stats = [], []
+        for s in self.scenes:
+            off = -1
+            if s._stats_dev is not None:
+                off = 4 * C * len(stats)
+                stats.append(s._stats_dev.reshape(-1))
+            rows.append([s.x.data_ptr(), s.y.data_ptr(), 0 if s.ref is None else s.ref.data_ptr(),
+                         0 if s.region is None else s.region.data_ptr(), s.grid.ysize, s.grid.xsize, off,
+                         (s.ref_type or 0) | ((s.region_type or 0) << 32)])
+        # scenes without statistics keep offset -1; the array is indexed by the offsets alone, padded to S rows for the check
+        pad = [torch.zeros(4 * C, dtype=torch.float64, device=self.device)] * (len(self.scenes) - len(stats))
+        self._stats_dev = torch.cat(stats + pad) if stats else None
+        self._descs = torch.from_numpy(np.array(rows, dtype=np.int64)).to(self.device)
+
+    def __len__(self):
+        return int(sum(self.numlist))
+
+    def locate(self, item):
+        """global item -> (scene index, item within the scene)  (data_utils.py:375-376)."""
+        item = int(item)
+        if item >= self.cumlen[-1] or item < 0:
+            raise IndexError('item exceeds the len')
+        ds = int(np.where(np.array(self.cumlen) > item)[0][0])
+        return ds, (item - self.cumlen[ds - 1] if ds > 0 else item)
+
+    def eff_range(self, item):
+        ds, cur = self.locate(item)
+        return self.scenes[ds].grid.eff_range(cur)
+
+    def index(self, items):
+        """The validated device copy of a list of global items (``_ops.TileIndex``): one upload, sliceable."""
+        from . import _ops as ops
+        return items if isinstance(items, ops.TileIndex) else ops.TileIndex(items, len(self.table), self.device)
+
+    def rects(self, index, n=None):
+        """The metric's rectangles (``eff_range``) of the first ``n`` tiles of ``index``, resident (``Evaluator.add_tiles``)."""
+        from . import _ops as ops
+        return ops.DeviceRects(self.table, self.index(index), n)
+
+    def cut(self, items, raw=False, out=None, want_valid=True):
+        """``(x, y, ref, region, valid)`` of the global ``items`` (a list, or the ``TileIndex`` :meth:`index` returns), all on the
+        device: x, y, ref as ``MultiSceneDataset([RegionTileDataset...])[i]`` returns them (each tile normalised with its own
+        scene's statistics; ``raw=True``: plain samples), ``region`` binarised like data_utils.py:280, ``valid`` the window
+        mask of ``raw_item``.  A scene without a reference / region map gives zero tiles."""
+        from . import _ops as ops
+        return ops.scene_set_cut(self._descs, self.table, self.index(items), self.bands, self.sample_type,
+                                 stats=None if raw else self._stats_dev, want_valid=want_valid, out=out)
+
+    def epoch(self, batch_size, seed, shuffle=True, ragged='pad', rank=None, world=None):
+        """An iterable with ``demos._Epoch``'s contract, ``((x, y, item, ref[, region]), n_real, weight)`` -- ``region`` when a
+        scene of the set has one, ``item`` a CPU int64 tensor, ``weight`` an ``EpochWeight`` -- over the batches, pads and
+        scales of ``dp.RankStridedBatches`` with the same seed."""
+        return _ResidentEpoch(self, batch_size, seed, shuffle, ragged, rank, world)
+
+
+class _ResidentEpoch:
+    def __init__(self, scene_set, batch_size, seed, shuffle, ragged, rank, world):
+        self.set = scene_set
+        self.args = (len(scene_set), batch_size, seed, shuffle, ragged, rank, world)
+
+    def __len__(self):
+        return len(EpochPlan(*self.args))
+
+    def __iter__(self):
+        # the whole plan is known here: this rank's index list goes up ONCE (pinned, asynchronous) and every batch is cut from a
+        # slice of it -- inside the epoch there is no host-to-device copy and nothing that makes the host wait for the device
+        plan = EpochPlan(*self.args)
+        index = self.set.index(plan.flat) if plan.flat else None
+        return self._batches(plan, index)
+
+    def _batches(self, plan, index):
+        s = self.set
+        for b, items in enumerate(plan.batches):
+            part = index[plan.offsets[b]:plan.offsets[b + 1]]
+            x, y, ref, region, _ = s.cut(part, want_valid=False)
+            real = len(items) - plan.pads[b]
+            w = EpochWeight(real / float(plan.n))
+            w.loss_scale = plan.scales[b]
+            w.rects = s.rects(part, real) if real > 0 else None
+            item = torch.tensor(items, dtype=torch.int64)
+            yield ((x, y, item, ref, region) if s.has_region else (x, y, item, ref)), real, w
 
 
 # ------------------------------------------------------------------------ dataset statistics
@@ -435,6 +652,20 @@ def dataset_meanstd(txt_x, txt_y, dataset):
         _write_stats(txt_x, mx, sx)
         _write_stats(txt_y, my, sy)
         return mx.numpy().tolist(), sx.numpy().tolist(), my.numpy().tolist(), sy.numpy().tolist()
+    mx, sx = _read_stats(txt_x)
+    my, sy = _read_stats(txt_y)
+    return mx, sx, my, sy
+
+
+def scene_meanstd(txt_x, txt_y, scene, overlap_padding=(0, 0)):
+    """``dataset_meanstd`` for a ``ResidentScene``: ``(meanX, stdX, meanY, stdY)`` as lists of floats, cached in the same two
+    text files -- read back when both exist, else taken on the device (``scene.statistics``) and written.  The values are
+    written with ``repr``, so reading them back is exact; files written by either function load in the other."""
+    if not (os.path.exists(txt_x) and os.path.exists(txt_y)):
+        mx, sx, my, sy = ([float(v) for v in a] for a in scene.statistics(overlap_padding))
+        _write_stats(txt_x, [repr(v) for v in mx], [repr(v) for v in sx])
+        _write_stats(txt_y, [repr(v) for v in my], [repr(v) for v in sy])
+        return mx, sx, my, sy
     mx, sx = _read_stats(txt_x)
     my, sy = _read_stats(txt_y)
     return mx, sx, my, sy

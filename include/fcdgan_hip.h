@@ -445,6 +445,47 @@ int fcd_scene_stitch(const float* cmap, const int32_t* table, int n, int ph, int
  * caller.  Writes no maps. */
 int fcd_tile_confusion(const float* cmap, const float* ref_tiles, const int32_t* rects, int n, int ph, int pw, float thresh,
                        float gt0, float gt1, float pre0, float pre1, unsigned long long* counts, void* stream);
+/* The same with the rectangles RESIDENT: rect_table = device int32 (T,4), validated by the caller at its one upload; tile t of
+ * cmap / ref_tiles takes row index[t] (device int32[n], every entry in [0,T): validated by the caller before upload; an entry
+ * outside the table counts nothing).  The training loop's metric then needs no host-to-device copy per batch. */
+int fcd_tile_confusion_items(const float* cmap, const float* ref_tiles, const int32_t* rect_table, int T, const int32_t* index,
+                             int n, int ph, int pw, float thresh, float gt0, float gt1, float pre0, float pre1,
+                             unsigned long long* counts, void* stream);
+
+/* ---- device-resident training feed (csrc/scene.hip) ---------------------------
+ * One row per resident scene of a set: device addresses of scene x, scene y (C*H*W samples of the set's sample type), the
+ * reference map and the region map (H*W samples of ref_type / region_type; address 0 = absent: zero tiles), the scene size,
+ * and the offset (in doubles) of this scene's meanX[C], stdX[C], meanY[C], stdY[C] in the statistics array, or -1 for
+ * plain samples.  64 bytes. */
+typedef struct fcd_scene_desc {
+  uint64_t x, y, ref, region;
+  int64_t H, W, stats_off;
+  int32_t ref_type, region_type;
+} fcd_scene_desc;
+/* fcd_scene_cut for tiles drawn from S resident scenes of different (H,W) in ONE launch -- the training-time cut
+ * (GDALDataset_RSS.__getitem__ over OSCD_Dataset_RSS, data_utils.py:239-290,375-388).  descs: S rows on the device.
+ * table: device int32 (T,13) = ALL tiles of the set, the 12 columns of the tile table + the scene index, every row validated
+ * by the caller against ITS scene before the one upload.  index: device int32[n] of rows of that table (the batch), every
+ * entry in [0,T), validated by the caller before upload; an entry outside the table gives a zero tile.
+ * x, y: n*C*ph*pw floats; ref_tiles, region_tiles, valid (each optional): n*ph*pw floats.  x, y, ref_tiles, valid are what
+ * fcd_scene_cut writes, normalised with the tile's OWN scene's statistics when stats is given; region_tiles follow
+ * data_utils.py:280: a sample > 125 becomes 1, any other sample keeps its value, the zero padding stays 0.  Every canvas
+ * element is written. */
+int fcd_scene_set_cut(const fcd_scene_desc* descs, int S, int sample_type, int C, const int32_t* table, int T,
+                      const int32_t* index, int n, int ph, int pw, const double* stats, float* x, float* y, float* ref_tiles,
+                      float* region_tiles, float* valid, void* stream);
+/* Masked per-band moments of a resident scene pair over the read rectangles of a tile table (CommonFunc.Dataset_mean /
+ * Dataset_std, CommonFunc.py:436-500).  A pixel is valid when the fp32 sum of the bands of scene_x, in band order, is
+ * non-zero (a NaN sum is valid); the same mask serves both scenes; a pixel read by two tiles counts twice.  C <= 32.
+ *   uint8 / uint16: out = 1 + 4*C unsigned 64-bit integers: n, sum x[C], sum x^2[C], sum y[C], sum y^2[C] -- exact, so
+ *     independent of summation order; n*ph*pw*max^2 must stay below 2^64 (checked).  No workspace.
+ *   float32: out = 1 + 4*C doubles: n, meanX[C], meanY[C], sum (x - meanX)^2[C], sum (y - meanY)^2[C]; two passes in fp64
+ *     (the deviations are taken about the fp64 mean), per-workgroup partials in ws (fcd_scene_stats_ws_bytes) folded in
+ *     index order, no floating-point atomics: two runs agree bit for bit.
+ * out is written, not accumulated. */
+size_t fcd_scene_stats_ws_bytes(int sample_type, int C, int n, int ph);
+int fcd_scene_stats(const void* scene_x, const void* scene_y, int sample_type, int C, int H, int W, const int32_t* table,
+                    int n, int ph, int pw, void* out, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- loss terms ------------------------------------------------------------
  * Masked per-sample sums -- the reconstruction terms of Loss.py:76-84 (L1) and
