@@ -170,6 +170,10 @@ _SIGS = {
     'fcd_scene_set_cut': (c_int, [P, c_int, c_int, c_int, P, c_int, P, c_int, c_int, c_int, P, P, P, P, P, P, P]),
     'fcd_scene_stats_ws_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
     'fcd_scene_stats': (c_int, [P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, P, P, c_size_t, P]),
+    'fcd_scene_set_cut_aug': (c_int, [P, c_int, c_int, c_int, P, c_int, P, c_int, c_int, c_int, P, c_int, c_double, c_double, P, c_int,
+                                      P, P, P, P, P, P]),
+    'fcd_scene_minmax_ws_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'fcd_scene_minmax': (c_int, [P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     'fcd_masked_recon_ws_bytes': (c_size_t, [c_int]),
     'fcd_masked_recon_fwd': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
     'fcd_masked_recon_bwd': (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),

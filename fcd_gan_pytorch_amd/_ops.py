@@ -1448,8 +1448,9 @@ class TileTable:
     :meth:`to`, the device copy the kernels read.  Only :func:`scene_tile_table` makes one, so a kernel never sees a row that
     was not checked on the host."""
 
-    def __init__(self, rows, geom):
+    def __init__(self, rows, geom, items=None):
         self.rows, self.geom, self._dev = rows, tuple(geom), {}
+        self.items = items            # the tile indices the rows were made from (None: rows of unknown origin)
 
     def __len__(self):
         return self.rows.shape[0]
@@ -1493,10 +1494,11 @@ def scene_tile_table(grid, items):
     tiling arithmetic, so the reference's border rule stays in one place -- and validated there (:func:`validate_tile_rows`)
     before anything is uploaded."""
     import numpy as np
-    rows = np.array([sum((list(t) for t in grid.slices(int(i))), []) for i in items], dtype=np.int64).reshape(-1, 12)
+    items = [int(i) for i in items]
+    rows = np.array([sum((list(t) for t in grid.slices(i)), []) for i in items], dtype=np.int64).reshape(-1, 12)
     geom = (grid.xsize, grid.ysize, grid.patch_size[0], grid.patch_size[1], grid.pad[0], grid.pad[1])
     validate_tile_rows(rows, *geom)
-    return TileTable(np.ascontiguousarray(rows.astype(np.int32)), geom)
+    return TileTable(np.ascontiguousarray(rows.astype(np.int32)), geom, items)
 
 
 def _scene_tensor(t, name, sample_type=None):
@@ -1708,6 +1710,34 @@ def scene_stats(scene_x, scene_y, table, sample_type=None, out=None):
             np.sqrt(tot[1 + 3 * C:1 + 4 * C] / (cnt - 1)), cnt)
 
 
+@torch.no_grad()
+def scene_minmax(scene_x, scene_y, table, sample_type=None):
+    """``(minX, maxX, minY, maxY, n)``: the masked per-band extrema of a resident scene pair ``(C,H,W)`` over the read rectangles
+    of ``table`` as float64 arrays (exact: the samples are uint8, uint16 or float32) and the valid count -- the mask of
+    :func:`scene_stats` (band sum of scene x non-zero).  Float32 scenes: NaN samples are skipped, +-inf take part; a band without
+    a comparable sample returns (+inf, -inf)."""
+    import numpy as np
+    sx, st = _scene_tensor(scene_x, 'scene_x', sample_type)
+    sy, st_y = _scene_tensor(scene_y, 'scene_y', sample_type)
+    if sx.dim() != 3 or sx.shape != sy.shape or st != st_y:
+        raise _lib.FcdError('scene_minmax: the two scenes must be (C,H,W) tensors of one shape and sample type')
+    C, H, W = sx.shape
+    table = _table_for(table, W, H)
+    _, _, pw, ph, _, _ = table.geom
+    n, dev = len(table), sx.device
+    out = torch.empty(4 * C, dtype=torch.float32, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    nbytes = lib.fcd_scene_minmax_ws_bytes(C, n, ph)
+    ws = _ws(nbytes, dev) if nbytes else None
+    check(lib.fcd_scene_minmax(_p(sx), _p(sy), st, C, H, W, _p(table.to(dev)), n, ph, pw, _p(out), _p(count), _p(ws), nbytes,
+                               _stream()), 'fcd_scene_minmax')
+    cnt = int(count.cpu()[0]) & (2 ** 64 - 1)
+    if cnt < 1:
+        raise _lib.FcdError('scene_minmax: no valid pixel')
+    v = out.cpu().numpy().astype(np.float64).reshape(4, C)
+    return v[0], v[1], v[2], v[3], cnt
+
+
 def validate_set_rows(rows, sizes, pw, ph, padx, pady):
     """Raise FcdError unless every (T,13) row of a scene SET's tile table -- the 12 columns + the scene index -- names one of the
     ``sizes`` = [(W, H), ...] and passes :func:`validate_tile_rows` against THAT scene."""
@@ -1823,16 +1853,94 @@ class DeviceRects:
             raise _lib.FcdError('DeviceRects: n = %d with %d indices' % (self.n, len(index)))
 
 
+ERASE_MAX = 16           # FCD_ERASE_MAX: rectangles per tile
+
+
+class EraseRects:
+    """Validated erase rectangles of ``n`` tiles: ``rows`` = host int32 (n, R, 4) of (x, y, w, h) in tile coordinates, unused
+    slots zero (w == 0 or h == 0: empty).  :meth:`to` uploads them ONCE, from pinned memory without making the host wait;
+    ``rects[a:b]`` is a view of the host rows and of the device copy -- a batch of an epoch's plan.  Only :func:`erase_rects`
+    makes one, so the kernel never sees a rectangle that was not checked against the tile on the host."""
+
+    def __init__(self, rows, patch, dev=None):
+        self.rows, self.patch, self.dev = rows, tuple(patch), dev
+
+    @property
+    def R(self):
+        return self.rows.shape[1]
+
+    def __len__(self):
+        return self.rows.shape[0]
+
+    def to(self, device):
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise _lib.FcdError('fcd_gan_pytorch_amd: the erase rectangles go to a CUDA/ROCm device, not %s (no CPU fallback)' % device)
+        if self.dev is None and self.R > 0:
+            self.dev = torch.from_numpy(self.rows).pin_memory().to(device, non_blocking=True)
+        return self
+
+    def __getitem__(self, s):
+        if not isinstance(s, slice) or s.step not in (None, 1):
+            raise TypeError('EraseRects takes contiguous slices')
+        return EraseRects(self.rows[s], self.patch, None if self.dev is None else self.dev[s])
+
+    def on(self, device):
+        self.to(device)
+        if self.dev is not None and self.dev.device != torch.device(device) and torch.device(device).index is not None:
+            raise _lib.FcdError('erase rectangles live on %s, the tiles on %s' % (self.dev.device, device))
+        return self.dev
+
+
+def erase_rects(regions, n, R, patch, device=None):
+    """The :class:`EraseRects` of ``n`` tiles with ``R`` slots each from host regions, one entry per tile: what the erasers of
+    ``transforms`` return -- ``(x, y, w, h)`` (``RANDOM_ERASER``), a list of ``[x, y, w, h]`` (``RANDOM_ERASER_MULTI_REGION``) --
+    or None.  Raises FcdError unless there are exactly ``n`` entries of at most ``R <= 16`` rectangles, every one inside the
+    ``patch`` = (pw, ph) tile: 0 <= x, 0 <= y, w, h >= 0, x + w <= pw, y + h <= ph.  ``device``: upload at once."""
+    import numpy as np
+    n, R, (pw, ph) = int(n), int(R), (int(patch[0]), int(patch[1]))
+    if not 0 <= R <= ERASE_MAX:
+        raise _lib.FcdError('erase_rects: %d rectangles per tile, at most %d' % (R, ERASE_MAX))
+    regions = list(regions)
+    if len(regions) != n or n <= 0:
+        raise _lib.FcdError('erase_rects: %d regions for %d tiles' % (len(regions), n))
+    rows = np.zeros((n, R, 4), np.int64)
+    for t, reg in enumerate(regions):
+        if reg is None:
+            continue
+        reg = list(reg)
+        if len(reg) == 4 and not any(hasattr(v, '__len__') for v in reg):
+            reg = [reg]                                      # one bare rectangle
+        if len(reg) > R:
+            raise _lib.FcdError('erase_rects: tile %d has %d rectangles, the list holds %d per tile' % (t, len(reg), R))
+        for k, rect in enumerate(reg):
+            if len(rect) != 4 or any(int(v) != v for v in rect):
+                raise _lib.FcdError('erase_rects: tile %d: a rectangle is four integers (x, y, w, h), got %r' % (t, rect))
+            rows[t, k] = [int(v) for v in rect]
+    x, y, w, h = (rows[..., k] for k in range(4))
+    bad = (rows < 0).any(axis=2) | (x + w > pw) | (y + h > ph)
+    if bad.any():
+        t, k = (int(v) for v in np.argwhere(bad)[0])
+        raise _lib.FcdError('erase_rects: tile %d: rectangle %s has a negative entry or leaves the %dx%d tile'
+                            % (t, rows[t, k].tolist(), pw, ph))
+    out = EraseRects(np.ascontiguousarray(rows.astype(np.int32)), (pw, ph))
+    return out.to(device) if device is not None else out
+
+
 SCENE_DESC_COLS = 8      # fcd_scene_desc as int64 columns: x, y, ref, region, H, W, stats_off, ref_type | region_type << 32
 
 
 @torch.no_grad()
-def scene_set_cut(descs, table, index, C, sample_type, stats=None, want_ref=True, want_region=True, want_valid=True, out=None):
+def scene_set_cut(descs, table, index, C, sample_type, stats=None, want_ref=True, want_region=True, want_valid=True, out=None,
+                  mode=1, scale=(-1, 1), erase=None):
     """Cut the tiles ``index`` (a :class:`TileIndex` into ``table``, a :class:`SceneSetTable`) out of the resident scenes that
     ``descs`` describes -- device int64 (S, 8) rows of ``fcd_scene_desc``, built by ``tiles.ResidentSceneSet`` from the tensors it
     keeps alive -- in one launch.  ``stats``: device float64 tensor the descriptors' statistics offsets point into, or None
     for plain samples.  Returns ``(x, y, ref, region, valid)`` like :func:`scene_cut` (+ the region tiles of
-    ``RegionTileDataset``); ``out`` = such a tuple of preallocated contiguous tensors; every element is written."""
+    ``RegionTileDataset``); ``out`` = such a tuple of preallocated contiguous tensors; every element is written.
+    ``mode``: what ``stats`` means -- 1 NORMALIZE (meanX, stdX, meanY, stdY), 2 SCALE, 3 SCALE_NORM onto ``scale`` (loX, hiX, loY,
+    hiY), 0 nothing; ``erase``: the :class:`EraseRects` of the batch, blanked in x and y after the enhancement (the paired
+    RANDOM_ERASER).  With ``mode == 1`` and no ``erase`` this is fcd_scene_set_cut, else fcd_scene_set_cut_aug."""
     if not isinstance(table, SceneSetTable) or not isinstance(index, TileIndex) or index.size != len(table):
         raise _lib.FcdError('scene_set_cut: pass a SceneSetTable and a TileIndex validated against it')
     if not torch.is_tensor(descs) or not descs.is_cuda or descs.dtype != torch.int64 or descs.dim() != 2 or \
@@ -1860,6 +1968,20 @@ def scene_set_cut(descs, table, index, C, sample_type, stats=None, want_ref=True
                 raise _lib.FcdError('scene_set_cut: out %s must be a contiguous %s float32 tensor on %s' % (name, shape, dev))
     x, y, rtile, region, valid = out
     tab, _ = table.to(dev)
+    if mode not in (0, 1, 2, 3):
+        raise _lib.FcdError('scene_set_cut: mode %r (0 none, 1 normalize, 2 scale, 3 scale_norm)' % (mode,))
+    if mode != 1 or erase is not None:
+        e, R = None, 0
+        if erase is not None:
+            if not isinstance(erase, EraseRects) or len(erase) != n or erase.patch != (pw, ph):
+                raise _lib.FcdError('scene_set_cut: erase must be the EraseRects of these %d tiles of %dx%d (erase_rects)' % (n, pw, ph))
+            e, R = erase.on(dev), erase.R
+            if e is not None and not e.is_contiguous():
+                raise _lib.FcdError('scene_set_cut: the erase rectangles must be contiguous')
+        check(lib.fcd_scene_set_cut_aug(_p(descs), S, sample_type, C, _p(tab), len(table), _p(index.on(dev)), n, ph, pw, _p(s),
+                                        int(mode), float(scale[0]), float(scale[1]), _p(e), R, _p(x), _p(y), _p(rtile), _p(region),
+                                        _p(valid), _stream()), 'fcd_scene_set_cut_aug')
+        return out
     check(lib.fcd_scene_set_cut(_p(descs), S, sample_type, C, _p(tab), len(table), _p(index.on(dev)), n, ph, pw, _p(s), _p(x), _p(y),
                                 _p(rtile), _p(region), _p(valid), _stream()), 'fcd_scene_set_cut')
     return out

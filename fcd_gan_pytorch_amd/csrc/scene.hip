@@ -282,10 +282,29 @@ extern "C" int fcd_tile_confusion_items(const float* cmap, const float* ref_tile
 // table or a scene outside the descriptors (neither passes the host's validation) yields a zero tile instead of a wild read.
 enum { TS_SCENE = T_COLS, TS_COLS = T_COLS + 1 };
 
+// AUG (fcd_scene_set_cut_aug) adds two things to the x and y planes, nothing to where anything is read or written:
+//   * the enhancement MODE (FCD_ENHANCE_*: CommonFunc.NORMALIZE / SCALE / SCALE_NORM) applied to the scenes that have parameters
+//     (stats_off >= 0), in fp64 with true divisions in the order the host evaluates them (no reciprocal, no contraction), so that
+//     the fp32 result equals NumPy's float64 evaluation followed by .astype(float32) bit for bit;
+//   * up to FCD_ERASE_MAX rectangles per tile (x, y, w, h in tile coordinates; w == 0 or h == 0: empty slot), erase[(t*R + r)*4..]:
+//     a sample inside any of them is STORED as +0.0f whatever it was (RANDOM_ERASER's assignment).  Lane r holds rectangle r (one
+//     16-byte load per lane, issued before the table decode, which it does not depend on); the row test y <= j < y + h is a
+//     ballot -- a bit per rectangle in a scalar register, wave-uniform -- and the lanes test x <= i < x + w for the set bits only,
+//     with x and w read out of lane r (v_readlane).  Both tests are differences, so no sum of a validated rectangle can overflow.
+// AUG = false is the kernel of fcd_scene_set_cut, instruction for instruction what it was before the template.
+struct SceneAugArgs {
+  int mode, R;
+  double s0, s1;
+  const int32_t* erase;
+};
+
+template <bool AUG>
 __global__ __launch_bounds__(kBlock) void fcd_scene_set_cut_kernel(
     const fcd_scene_desc* __restrict__ descs, int S, int stype, int C, const int32_t* __restrict__ table, int T,
     const int32_t* __restrict__ index, int units, int ph, int pw, const double* __restrict__ stats, float* __restrict__ x,
-    float* __restrict__ y, float* __restrict__ ref_tiles, float* __restrict__ region_tiles, float* __restrict__ valid) {
+    float* __restrict__ y, float* __restrict__ ref_tiles, float* __restrict__ region_tiles, float* __restrict__ valid,
+    SceneAugArgs aug) {
+#pragma clang fp contract(off)
   const int lane = threadIdx.x & (FCD_WAVE - 1);
   const unsigned planes = 2 * C + (ref_tiles ? 1 : 0) + (region_tiles ? 1 : 0) + (valid ? 1 : 0);
   const int j = wave_row<kWaves>();
@@ -293,6 +312,13 @@ __global__ __launch_bounds__(kBlock) void fcd_scene_set_cut_kernel(
   for (unsigned pl = blockIdx.y; pl < (unsigned)units; pl += gridDim.y) {      // units = n * planes <= INT_MAX (checked by the host)
     const long long t = pl / planes;
     const int q = (int)(pl - (unsigned)t * planes);
+    // rectangles of this tile that cross this canvas row: one bit each (x and y planes only; lanes >= R hold an empty slot)
+    int4 rect = make_int4(0, 0, 0, 0);
+    unsigned long long hit = 0;
+    if (AUG && aug.R > 0 && q < 2 * C) {
+      if (lane < aug.R) rect = ((const int4*)aug.erase)[t * aug.R + lane];
+      hit = __ballot(rect.z > 0 && rect.w > 0 && j >= rect.y && j - rect.y < rect.w);
+    }
     const int g = index[t];
     const bool row_ok = g >= 0 && g < T;
     const int32_t* __restrict__ row = table + (long long)(row_ok ? g : 0) * TS_COLS;
@@ -317,11 +343,17 @@ __global__ __launch_bounds__(kBlock) void fcd_scene_set_cut_kernel(
     } else {
       ones = true; dst = valid + (t * ph + j) * pw;
     }
+    if (AUG && aug.mode == FCD_ENHANCE_NONE) norm = false;
     double mean = 0.0, stdv = 1.0;
-    if (norm) {          // this scene's meanX[C], stdX[C], meanY[C], stdY[C]
+    if (norm) {          // this scene's meanX[C], stdX[C], meanY[C], stdY[C] (AUG, modes 2 and 3: loX, hiX, loY, hiY)
       const double* __restrict__ st = stats + d->stats_off + (q < C ? 0 : 2 * C);
       mean = st[c]; stdv = st[C + c];
     }
+    // ONE division per sample whatever the mode (all of this is wave-uniform): the divisor is std, or hi - lo for the two scales;
+    // SCALE_NORM multiplies the numerator by s1 - s0 first and adds s0 last
+    const int mode = AUG ? aug.mode : FCD_ENHANCE_NORMALIZE;
+    const bool to_range = AUG && mode == FCD_ENHANCE_SCALE_NORM;
+    const double den = mode == FCD_ENHANCE_NORMALIZE ? stdv : stdv - mean, width = AUG ? aug.s1 - aug.s0 : 0.0;
     const bool live_plane = in_rows && (ones || src != nullptr);        // an absent map (address 0) gives zero tiles
     const long long sbase = ((long long)c * H + (ry + (j - wy))) * W + (rx - wx);
     for (int i = lane; i < pw; i += FCD_WAVE) {
@@ -331,9 +363,24 @@ __global__ __launch_bounds__(kBlock) void fcd_scene_set_cut_kernel(
           v = 1.f;
         } else {
           v = load_sample(src, sbase + i, type);
-          if (norm) v = (float)(((double)v - mean) / stdv);
+          if (norm) {
+            double e = (double)v - mean;
+            if (to_range) e = width * e;
+            e = e / den;
+            if (to_range) e = e + aug.s0;
+            v = (float)e;
+          }
           if (region && v > 125.f) v = 1.f;                  // data_utils.py:280
         }
+      }
+      if (AUG) {
+        bool gone = false;
+        for (unsigned long long m = hit; m; m &= m - 1) {    // wave-uniform trip count
+          const int r = __builtin_ctzll(m);
+          const int ex = __builtin_amdgcn_readlane(rect.x, r), ew = __builtin_amdgcn_readlane(rect.z, r);
+          gone = gone || (i >= ex && i - ex < ew);
+        }
+        if (gone) v = 0.f;                                   // an assignment: NaN and inf become +0 too
       }
       dst[i] = v;
     }
@@ -352,9 +399,34 @@ extern "C" int fcd_scene_set_cut(const fcd_scene_desc* descs, int S, int sample_
   const long long rows = units * ph;
   const double in_bytes = sample_type == FCD_SAMPLE_U8 ? 1.0 : sample_type == FCD_SAMPLE_U16 ? 2.0 : 4.0;
   FcdProfScope prof(FCD_K_MISC, (hipStream_t)stream, 0.0, (double)rows * pw * 4.0 + 2.0 * n * C * ph * pw * in_bytes);
-  hipLaunchKernelGGL(fcd_scene_set_cut_kernel, row_grid(ph, units), dim3(kBlock), 0, (hipStream_t)stream, descs, S, sample_type,
-                     C, table, T, index, (int)units, ph, pw, stats, x, y, ref_tiles, region_tiles, valid);
+  hipLaunchKernelGGL(fcd_scene_set_cut_kernel<false>, row_grid(ph, units), dim3(kBlock), 0, (hipStream_t)stream, descs, S,
+                     sample_type, C, table, T, index, (int)units, ph, pw, stats, x, y, ref_tiles, region_tiles, valid, SceneAugArgs{});
   FCD_LAUNCH_CHECK("fcd_scene_set_cut");
+  return FCD_OK;
+}
+
+extern "C" int fcd_scene_set_cut_aug(const fcd_scene_desc* descs, int S, int sample_type, int C, const int32_t* table, int T,
+                                     const int32_t* index, int n, int ph, int pw, const double* stats, int mode, double s0,
+                                     double s1, const int32_t* erase, int R, float* x, float* y, float* ref_tiles,
+                                     float* region_tiles, float* valid, void* stream) {
+  FCD_CHECK_ARG(descs && table && index && x && y && S > 0 && C > 0 && T > 0 && n > 0 && ph > 0 && pw > 0,
+                "fcd_scene_set_cut_aug: bad arguments");
+  FCD_CHECK_ARG(sample_type_ok(sample_type), "fcd_scene_set_cut_aug: sample type %d (0 uint8, 1 uint16, 2 float32)", sample_type);
+  FCD_CHECK_ARG(mode >= FCD_ENHANCE_NONE && mode <= FCD_ENHANCE_SCALE_NORM,
+                "fcd_scene_set_cut_aug: enhancement mode %d (0 none, 1 normalize, 2 scale, 3 scale_norm)", mode);
+  FCD_CHECK_ARG(R >= 0 && R <= FCD_ERASE_MAX, "fcd_scene_set_cut_aug: %d rectangles per tile, at most %d", R, FCD_ERASE_MAX);
+  FCD_CHECK_ARG((erase != nullptr) == (R > 0), "fcd_scene_set_cut_aug: the rectangle list goes with R > 0 (R = %d)", R);
+  FCD_CHECK_ARG(((uintptr_t)erase & 15) == 0, "fcd_scene_set_cut_aug: the rectangle list must be 16-byte aligned");
+  const int planes = 2 * C + (ref_tiles ? 1 : 0) + (region_tiles ? 1 : 0) + (valid ? 1 : 0);
+  const long long units = (long long)n * planes;
+  FCD_CHECK_ARG(units <= INT32_MAX, "fcd_scene_set_cut_aug: %d tiles x %d planes exceed 2^31 - 1", n, planes);
+  const long long rows = units * ph;
+  const double in_bytes = sample_type == FCD_SAMPLE_U8 ? 1.0 : sample_type == FCD_SAMPLE_U16 ? 2.0 : 4.0;
+  FcdProfScope prof(FCD_K_MISC, (hipStream_t)stream, 0.0, (double)rows * pw * 4.0 + 2.0 * n * C * ph * pw * in_bytes);
+  hipLaunchKernelGGL(fcd_scene_set_cut_kernel<true>, row_grid(ph, units), dim3(kBlock), 0, (hipStream_t)stream, descs, S,
+                     sample_type, C, table, T, index, (int)units, ph, pw, stats, x, y, ref_tiles, region_tiles, valid,
+                     SceneAugArgs{mode, R, s0, s1, erase});
+  FCD_LAUNCH_CHECK("fcd_scene_set_cut_aug");
   return FCD_OK;
 }
 
@@ -518,5 +590,153 @@ extern "C" int fcd_scene_stats(const void* scene_x, const void* scene_y, int sam
                      (long long)W, table, n, (const double*)(o + 1), ws);
   hipLaunchKernelGGL(fcd_scene_stats_fold_kernel, dim3(1), dim3(kBlock), 0, st, (const double*)ws, blocks, 2 * C, 0, o + 1 + 2 * C);
   FCD_LAUNCH_CHECK("fcd_scene_stats");
+  return FCD_OK;
+}
+
+// ---- extrema ---------------------------------------------------------------------------------------------------------
+// Masked per-band minimum and maximum of both scenes over the read rectangles of a tile table (CommonFunc.Dataset_maxmin,
+// CommonFunc.py:294-370), under the mask of the statistics: the fp32 band sum of scene x is non-zero.  The structure is the
+// statistics kernel's -- one wave per (tile, row), mask bits per 64 x 64-column segment, wave reduction (shuffles), the wave's OWN
+// slots in LDS, one partial row per workgroup -- with min / max in place of sums.  Every sample type goes through float: uint8 and
+// uint16 are exact there, so ONE kernel serves all three and there is no atomic of any kind; the partial rows (4*C floats and a
+// 64-bit count per workgroup) are folded by fcd_scene_minmax_fold_kernel.  A sample replaces the running extremum only when it
+// compares below / above it, so a NaN sample is skipped and +-inf take part; the running values start at +inf / -inf, which is what
+// a band without a single comparable sample returns.
+__device__ __forceinline__ float wave_min_f(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float u = __shfl_xor(v, o, 64);
+    v = u < v ? u : v;
+  }
+  return v;
+}
+__device__ __forceinline__ float wave_max_f(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float u = __shfl_xor(v, o, 64);
+    v = u > v ? u : v;
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(kCountBlock) void fcd_scene_minmax_kernel(
+    const void* __restrict__ sx, const void* __restrict__ sy, int stype, int C, long long H, long long W,
+    const int32_t* __restrict__ table, int n, float* __restrict__ part_out, unsigned long long* __restrict__ cnt_out) {
+  __shared__ float part[kCountWaves][4 * kStatBands];        // minX[C] maxX[C] minY[C] maxY[C] per wave: 8 KB
+  __shared__ unsigned long long pcnt[kCountWaves];
+  const int lane = threadIdx.x & (FCD_WAVE - 1);
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int j = wave_row<kCountWaves>();
+  const int slots = 4 * C;
+  for (int k = lane; k < slots; k += FCD_WAVE) part[w][k] = ((k / C) & 1) ? -INFINITY : INFINITY;
+  if (lane == 0) pcnt[w] = 0;
+  __syncthreads();
+  for (long long t = blockIdx.y; t < n; t += gridDim.y) {    // no early return: every wave reaches the barrier below
+    const int32_t* __restrict__ row = table + t * T_COLS;
+    const int rx = row[T_RX], ry = row[T_RY], rw = row[T_RW], rh = row[T_RH];
+    if (j >= rh) continue;                                    // wave-uniform
+    const long long rbase = (long long)(ry + j) * W + rx;    // first sample of this row in band 0
+    for (int seg = 0; seg < rw; seg += kStatSegment) {
+      const int chunks = std::min(64, (rw - seg + FCD_WAVE - 1) / FCD_WAVE);
+      unsigned long long bits = 0;                           // bit k: column seg + 64 k + lane is valid
+      for (int k = 0; k < chunks; ++k) {
+        const int i = seg + k * FCD_WAVE + lane;
+        if (i < rw) {
+          float s = 0.f;
+          for (int c = 0; c < C; ++c) s += load_sample(sx, (long long)c * H * W + rbase + i, stype);
+          if (s != 0.f) bits |= 1ull << k;
+        }
+      }
+      const unsigned long long cnt = wave_sum_u64((unsigned long long)__popcll(bits));
+      if (lane == 0) pcnt[w] += cnt;
+      for (int c = 0; c < C; ++c) {
+        float x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
+        const long long cbase = (long long)c * H * W + rbase;
+        for (int k = 0; k < chunks; ++k) {
+          if (!((bits >> k) & 1)) continue;
+          const int i = seg + k * FCD_WAVE + lane;
+          const float vx = load_sample(sx, cbase + i, stype), vy = load_sample(sy, cbase + i, stype);
+          x0 = vx < x0 ? vx : x0; x1 = vx > x1 ? vx : x1;
+          y0 = vy < y0 ? vy : y0; y1 = vy > y1 ? vy : y1;
+        }
+        x0 = wave_min_f(x0); x1 = wave_max_f(x1); y0 = wave_min_f(y0); y1 = wave_max_f(y1);
+        if (lane == 0) {
+          part[w][c] = x0 < part[w][c] ? x0 : part[w][c];
+          part[w][C + c] = x1 > part[w][C + c] ? x1 : part[w][C + c];
+          part[w][2 * C + c] = y0 < part[w][2 * C + c] ? y0 : part[w][2 * C + c];
+          part[w][3 * C + c] = y1 > part[w][3 * C + c] ? y1 : part[w][3 * C + c];
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const long long block = (long long)blockIdx.y * gridDim.x + blockIdx.x;
+  if ((int)threadIdx.x < slots) {
+    const bool is_max = ((int)threadIdx.x / C) & 1;
+    float v = part[0][threadIdx.x];
+    for (int k = 1; k < kCountWaves; ++k) {
+      const float u = part[k][threadIdx.x];
+      v = is_max ? (u > v ? u : v) : (u < v ? u : v);
+    }
+    part_out[block * slots + threadIdx.x] = v;
+  } else if ((int)threadIdx.x == slots) {                    // slots <= 128 < the block size
+    unsigned long long s = 0;
+    for (int k = 0; k < kCountWaves; ++k) s += pcnt[k];
+    cnt_out[block] = s;
+  }
+}
+
+// out[k] = min / max over the workgroups' partial rows (rows 0 and 2 of the (4,C) result are minima), count = sum of their counts.
+// One wave per output: the lanes stride over the partial rows (a few loads each, all in flight together) and reduce by shuffles;
+// workgroup 4*C folds the counts.
+__global__ __launch_bounds__(FCD_WAVE) void fcd_scene_minmax_fold_kernel(const float* __restrict__ partials,
+                                                                        const unsigned long long* __restrict__ counts, int blocks,
+                                                                        int C, float* __restrict__ out,
+                                                                        unsigned long long* __restrict__ count) {
+  const int k = blockIdx.x, slots = 4 * C, lane = threadIdx.x;
+  if (k < slots) {
+    const bool is_max = (k / C) & 1;                         // uniform over the workgroup
+    float v = is_max ? -INFINITY : INFINITY;
+    for (int b = lane; b < blocks; b += FCD_WAVE) {
+      const float u = partials[(long long)b * slots + k];
+      v = is_max ? (u > v ? u : v) : (u < v ? u : v);
+    }
+    v = is_max ? wave_max_f(v) : wave_min_f(v);
+    if (lane == 0) out[k] = v;
+  } else {
+    unsigned long long s = 0;
+    for (int b = lane; b < blocks; b += FCD_WAVE) s += counts[b];
+    s = wave_sum_u64(s);
+    if (lane == 0) *count = s;
+  }
+}
+
+// workspace: blocks x 4*C floats (16*C bytes per row: the counts behind them stay 8-byte aligned), then blocks x one 64-bit count
+extern "C" size_t fcd_scene_minmax_ws_bytes(int C, int n, int ph) {
+  if (C <= 0 || C > kStatBands || n <= 0 || ph <= 0) return 0;
+  return (size_t)stats_blocks(n, ph) * ((size_t)4 * C * sizeof(float) + sizeof(unsigned long long));
+}
+
+extern "C" int fcd_scene_minmax(const void* scene_x, const void* scene_y, int sample_type, int C, int H, int W,
+                                const int32_t* table, int n, int ph, int pw, float* out, unsigned long long* count, void* ws,
+                                size_t ws_bytes, void* stream) {
+  FCD_CHECK_ARG(scene_x && scene_y && table && out && count && C > 0 && H > 0 && W > 0 && n > 0 && ph > 0 && pw > 0,
+                "fcd_scene_minmax: bad arguments");
+  FCD_CHECK_ARG(sample_type_ok(sample_type), "fcd_scene_minmax: sample type %d (0 uint8, 1 uint16, 2 float32)", sample_type);
+  FCD_CHECK_ARG(C <= kStatBands, "fcd_scene_minmax: %d bands, at most %d", C, kStatBands);
+  const size_t need = fcd_scene_minmax_ws_bytes(C, n, ph);
+  FCD_CHECK_ARG(ws && ws_bytes >= need, "fcd_scene_minmax: workspace of %zu bytes, %zu needed", ws_bytes, need);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid = count_grid(ph, n);
+  const int blocks = (int)(grid.x * grid.y);
+  float* parts = (float*)ws;
+  unsigned long long* counts = (unsigned long long*)((char*)ws + (size_t)blocks * 4 * C * sizeof(float));
+  const double bytes = (double)n * ph * pw * (3.0 * C) * (sample_type == FCD_SAMPLE_U8 ? 1.0 : sample_type == FCD_SAMPLE_U16 ? 2.0 : 4.0);
+  FcdProfScope prof(FCD_K_MISC, st, 0.0, bytes);
+  hipLaunchKernelGGL(fcd_scene_minmax_kernel, grid, dim3(kCountBlock), 0, st, scene_x, scene_y, sample_type, C, (long long)H,
+                     (long long)W, table, n, parts, counts);
+  hipLaunchKernelGGL(fcd_scene_minmax_fold_kernel, dim3(4 * C + 1), dim3(FCD_WAVE), 0, st, (const float*)parts,
+                     (const unsigned long long*)counts, blocks, C, out, count);
+  FCD_LAUNCH_CHECK("fcd_scene_minmax");
   return FCD_OK;
 }

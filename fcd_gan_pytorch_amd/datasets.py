@@ -23,8 +23,8 @@ from . import tiles
 
 class RegionTileDataset(tiles.PairTileDataset):
     def __init__(self, scene_x, scene_y, region=None, ref=None, patch_size=(200, 200), overlap_padding=(10, 10),
-                 stats=None):
-        super().__init__(scene_x, scene_y, ref, patch_size, overlap_padding, stats)
+                 stats=None, enhance=None, transforms=None):
+        super().__init__(scene_x, scene_y, ref, patch_size, overlap_padding, stats, enhance, transforms)
         if isinstance(region, str):
             region = tiles.read_tiff(region)
         if region is not None and (region.shape[0] != 1 or region.shape[1:] != self.x.shape[1:]):

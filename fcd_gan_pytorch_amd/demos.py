@@ -13,6 +13,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from . import Loss, Module, dp, metrics, optim, steps, tiles
+from . import transforms as _transforms
 
 
 class _Epoch:
@@ -72,12 +73,21 @@ def _tile_stats(scene_x, scene_y, patch_size, stats_txt=None):
     return tuple(v.double().numpy() for v in (mx, sx, my, sy))
 
 
+def _tile_ranges(scene_x, scene_y, patch_size, stats_txt=None):
+    """Dataset_maxmin over the NON-overlapped tiling of the scene pair (Demo_RSSS.py:91-96): two lists of [min, max] per band,
+    cached in the reference's two text files when ``stats_txt=(path_x, path_y)``."""
+    ds = tiles.PairTileDataset(scene_x, scene_y, None, patch_size, (0, 0))
+    if stats_txt:
+        return tiles.dataset_maxmin(stats_txt[0], stats_txt[1], ds)
+    return tiles._fold_maxmin(ds)
+
+
 def demo_usss(scene_x, scene_y, ref=None, device='cuda', patch_size=(220, 220), overlap_padding=(10, 10),
               epochs_g=50, epochs_s=50, epochs_joint=100, batch_size=10, learning_rate=2e-4,
               perception_weight=0.4, l1_weight=0.65, ssim_weight=0, perception_perBand=True,
               prob_thresh=0.5, gt_map=(1, 2), pre_map=(0, 1), seed=0, out_density=None, out_color=None,
               log=None, allow_seeded=False, stats_txt=None, save_s=None, save_g=None, ragged='pad', resident_inference=False,
-              resident_training=False):
+              resident_training=False, enhance='normalize', scale_range=(-1, 1), transforms=None):
     """Demo_USSS.py:29-501: G pre-train -> S pre-train -> joint training -> inference with centre write-back, with the
     reference's LR schedules (Demo_USSS.py:133,201,298-299) and per-tile dataset statistics (:88-95).
     ``scene_x/scene_y/ref``: (bands,H,W) arrays or TIFF paths; ``save_s`` / ``save_g``: ``.pkl`` paths
@@ -88,6 +98,12 @@ def demo_usss(scene_x, scene_y, ref=None, device='cuda', patch_size=(220, 220), 
     training phases (``ResidentSceneSet.epoch``: same batches, tiles bit-identical for the same statistics), the joint phase's
     accuracy (counted over each tile's owned centre, ``Evaluator.add_tiles`` on resident rectangles -- with overlapped tiles
     the host route counts the context ring too) and the final inference.
+    ``enhance``: 'normalize' (NORMALIZE with the tile statistics), or the reference's alternative pre-processing 'scale' /
+    'scale_norm' (``transforms.SCALE`` / ``SCALE_NORM`` onto ``scale_range``) with the per-band ranges of
+    ``tiles.dataset_maxmin`` (host route) or ``scene.maxmin()`` (resident route), cached through ``stats_txt`` when given; both
+    training routes and both inference routes use the same enhancer.  ``transforms``: a ``transforms.RANDOM_ERASER`` /
+    ``RANDOM_ERASER_MULTI_REGION`` for the TRAINING tiles only (drawn per tile on the host route, per epoch plan on the resident
+    one); inference never erases.
     Returns dict(netS, netG, density (1,H,W) float32, color (1,H,W), evaluator, history, vgg_pretrained)."""
     dev = torch.device(device)
     if isinstance(scene_x, str):
@@ -96,18 +112,32 @@ def demo_usss(scene_x, scene_y, ref=None, device='cuda', patch_size=(220, 220), 
         scene_y = tiles.read_tiff(scene_y)
     if isinstance(ref, str):
         ref = tiles.read_tiff(ref)
-    scene = None
+    if enhance not in ('normalize', 'scale', 'scale_norm'):
+        raise ValueError("enhance: 'normalize', 'scale' or 'scale_norm', got %r" % (enhance,))
+    scene, stats, enh = None, None, None
     if resident_training:
         scene = tiles.ResidentScene(scene_x, scene_y, ref, patch_size, overlap_padding, device=dev)
-        stats = tiles.scene_meanstd(stats_txt[0], stats_txt[1], scene) if stats_txt else scene.statistics()
-        stats = tuple(np.asarray(v, np.float64) for v in stats)
-        scene.set_stats(stats)
-        feed = tiles.ResidentSceneSet([scene])
+        if enhance == 'normalize':
+            stats = tiles.scene_meanstd(stats_txt[0], stats_txt[1], scene) if stats_txt else scene.statistics()
+            stats = tuple(np.asarray(v, np.float64) for v in stats)
+            scene.set_stats(stats)
+        else:
+            r1, r2 = tiles.scene_maxmin(stats_txt[0], stats_txt[1], scene) if stats_txt else scene.maxmin()
+            enh = _transforms.enhancer(enhance, r1, r2, scale_range)
+            scene.set_enhance(enh)
+        feed = tiles.ResidentSceneSet([scene], transforms=transforms)
         epoch = lambda sd: feed.epoch(batch_size, sd, ragged=ragged)
     else:
-        stats = _tile_stats(scene_x, scene_y, patch_size, stats_txt)
-        epoch = lambda sd: _Epoch(ds, batch_size, sd, dev, ragged=ragged)
-    ds = tiles.PairTileDataset(scene_x, scene_y, ref, patch_size, overlap_padding, stats=stats)
+        if enhance == 'normalize':
+            stats = _tile_stats(scene_x, scene_y, patch_size, stats_txt)
+        else:
+            r1, r2 = _tile_ranges(scene_x, scene_y, patch_size, stats_txt)
+            enh = _transforms.enhancer(enhance, r1, r2, scale_range)
+        epoch = lambda sd: _Epoch(train_ds, batch_size, sd, dev, ragged=ragged)
+    ds = tiles.PairTileDataset(scene_x, scene_y, ref, patch_size, overlap_padding, stats=stats, enhance=enh)
+    # the erasers augment the training tiles only: inference reads ``ds``, which never has them
+    train_ds = ds if transforms is None else tiles.PairTileDataset(scene_x, scene_y, ref, patch_size, overlap_padding,
+                                                                   stats=stats, enhance=enh, transforms=transforms)
     nband = scene_x.shape[0]
     torch.manual_seed(seed)
     netS = Module.Segmentor(n_channels=nband, bilinear=True).to(dev)
@@ -161,7 +191,7 @@ def demo_usss(scene_x, scene_y, ref=None, device='cuda', patch_size=(220, 220), 
     dp.sync_buffers((netS, netG))            # one set of BatchNorm statistics for the stitched map AND the checkpoint
     if resident_inference:
         if scene is None:
-            scene = tiles.ResidentScene(scene_x, scene_y, ref, patch_size, overlap_padding, stats=stats, device=dev)
+            scene = tiles.ResidentScene(scene_x, scene_y, ref, patch_size, overlap_padding, stats=stats, device=dev, enhance=enh)
         res = infer_scene_resident(netS, scene, dev, batch_size=batch_size, prob_thresh=prob_thresh, gt_map=gt_map,
                                    pre_map=pre_map)
     else:

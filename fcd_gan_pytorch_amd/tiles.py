@@ -227,7 +227,9 @@ class PairTileDataset(torch.utils.data.Dataset):
     reference's tuple ``(x, y, item, ref)`` of float32 tensors (data_utils.py:140)."""
 
     def __init__(self, scene_x, scene_y, ref=None, patch_size=(200, 200), overlap_padding=(10, 10),
-                 stats=None):
+                 stats=None, enhance=None, transforms=None):
+        if stats is not None and enhance is not None:
+            raise ValueError('PairTileDataset: give stats (NORMALIZE) or enhance, not both')
         if isinstance(scene_x, str):
             scene_x = read_tiff(scene_x)
         if isinstance(scene_y, str):
@@ -241,6 +243,10 @@ class PairTileDataset(torch.utils.data.Dataset):
         self.x, self.y, self.ref = scene_x, scene_y, ref
         self.grid = TileGrid(scene_x.shape[2], scene_x.shape[1], patch_size, overlap_padding)
         self.stats = stats            # (meanX, stdX, meanY, stdY) per band, NORMALIZE semantics
+        # the reference's two hooks (data_utils.py:110-112,126-128): ``enhance(block, switch=1 | 2)`` on the read block in float64
+        # (a ``transforms.NORMALIZE`` / ``SCALE`` / ``SCALE_NORM``), ``transforms`` on the two float32 tensors after placement
+        # (a ``transforms.RANDOM_ERASER...``: the region drawn for x is reused for y)
+        self.enhance, self.transforms = enhance, transforms
 
     def __len__(self):
         return len(self.grid)
@@ -255,7 +261,10 @@ class PairTileDataset(torch.utils.data.Dataset):
         """The patch WITHOUT host normalisation: ``(x_raw, y_raw, item, ref, valid)`` with ``valid`` (1,py,px) = 1 on
         the window that holds scene pixels.  Normalise on the device (``_ops.normalize_tiles``: one fused pass, fp64 per
         element, bit-identical to ``__getitem__``) or not at all (``Segmentor.forward_raw`` folds the statistics into
-        its first convolution)."""
+        its first convolution).  Not with ``transforms``: erasing raw samples before the device normalises them would not
+        give the zeros the reference trains on."""
+        if self.transforms is not None:
+            raise ValueError('raw_item: a dataset with transforms has no raw route (erase after normalisation)')
         _, (rx, ry, rw, rh), (wx, wy, ww, wh) = self.grid.slices(item)
         px, py = self.grid.patch_size
         cx = np.zeros((self.x.shape[0], py, px), dtype=np.float32)
@@ -277,6 +286,9 @@ class PairTileDataset(torch.utils.data.Dataset):
         if self.stats is not None:                      # 'enhance' runs on the read block (data_utils.py:106-108)
             bx = self._norm(bx, self.stats[0], self.stats[1])
             by = self._norm(by, self.stats[2], self.stats[3])
+        if self.enhance is not None:
+            bx = self.enhance(bx, switch=1)
+            by = self.enhance(by, switch=2)
         px, py = self.grid.patch_size
         cx = np.zeros((bx.shape[0], py, px), dtype=float)
         cy = np.zeros_like(cx)
@@ -285,8 +297,11 @@ class PairTileDataset(torch.utils.data.Dataset):
         r = np.zeros((1, py, px), dtype=float)
         if self.ref is not None:
             r[:, wy:wy + wh, wx:wx + ww] = self.ref[:, ry:ry + rh, rx:rx + rw]
-        return (torch.from_numpy(cx).float(), torch.from_numpy(cy).float(), torch.tensor(item),
-                torch.from_numpy(r).float())
+        tx, ty = torch.from_numpy(cx).float(), torch.from_numpy(cy).float()
+        if self.transforms is not None:
+            tx, sync = self.transforms(tx)
+            ty, _ = self.transforms(ty, sync)
+        return tx, ty, torch.tensor(item), torch.from_numpy(r).float()
 
 
 class RawTiles(torch.utils.data.Dataset):
@@ -312,8 +327,10 @@ class ResidentScene:
     device before anything is cut."""
 
     def __init__(self, scene_x, scene_y, ref=None, patch_size=(200, 200), overlap_padding=(10, 10), stats=None, device='cuda',
-                 region=None):
+                 region=None, enhance=None):
         from . import _ops as ops
+        if stats is not None and enhance is not None:
+            raise ValueError('ResidentScene: give stats (NORMALIZE) or enhance, not both')
         if isinstance(scene_x, str):
             scene_x = read_tiff(scene_x)
         if isinstance(scene_y, str):
@@ -349,6 +366,8 @@ class ResidentScene:
                      ops.SAMPLE_F32, None if region is None else up(region),
                      0 if region is None else {1: ops.SAMPLE_U8, 2: ops.SAMPLE_U16, 4: ops.SAMPLE_F32}[region.dtype.itemsize],
                      patch_size, overlap_padding, stats)
+        if enhance is not None:
+            self.set_enhance(enhance)
 
     @classmethod
     def from_device(cls, x, y, ref=None, region=None, patch_size=(200, 200), overlap_padding=(10, 10), stats=None,
@@ -381,6 +400,7 @@ class ResidentScene:
         self.bands = int(x.shape[0])
         self.grid = TileGrid(int(x.shape[2]), int(x.shape[1]), patch_size, overlap_padding)
         self.stats, self._stats_dev, self.stats_count = None, None, None
+        self.enhance, self.enhance_kind, self.enhance_scale, self._solo = None, 0, None, None
         if isinstance(stats, str):
             if stats != 'auto':
                 raise ValueError("stats: (meanX, stdX, meanY, stdY), None or 'auto'")
@@ -391,11 +411,40 @@ class ResidentScene:
         """``stats`` = (meanX, stdX, meanY, stdY) per band, NORMALIZE semantics (as PairTileDataset), or None."""
         from . import _ops as ops
         self.stats, self._stats_dev = stats, None
+        self.enhance, self.enhance_kind, self.enhance_scale, self._solo = None, 0, None, None
         if stats is not None:
             s = np.stack([np.asarray(v, dtype=np.float64).reshape(-1) for v in stats])
             if s.shape != (4, self.bands):
                 raise ops._lib.FcdError("ResidentScene: The input channel doesn't match the stats list")   # CommonFunc.py:212
             self._stats_dev = torch.from_numpy(np.ascontiguousarray(s)).to(self.device)
+            self.enhance_kind = 1
+
+    def set_enhance(self, enh):
+        """``enh`` = a ``transforms.NORMALIZE`` / ``SCALE`` / ``SCALE_NORM`` (the object ``PairTileDataset(enhance=)`` takes), or
+        None.  ``NORMALIZE`` is ``set_stats`` with its four lists; the other two put their per-band ranges where the statistics
+        go and switch the cut to their formula (``_ops.scene_set_cut(mode=)``)."""
+        if enh is None or enh.kind == 1:
+            self.set_stats(None if enh is None else tuple(np.asarray(v, np.float64) for v in enh.params(self.bands)))
+            self.enhance = enh
+            return
+        self.set_stats(None)
+        self._stats_dev = torch.from_numpy(np.ascontiguousarray(enh.params(self.bands))).to(self.device)
+        self.enhance, self.enhance_kind = enh, int(enh.kind)
+        self.enhance_scale = (float(enh.scale[0]), float(enh.scale[1])) if enh.kind == 3 else None
+
+    def maxmin(self, overlap_padding=(0, 0)):
+        """Two lists of ``[min, max]`` per band, of scene x and of scene y: the TRUE masked extrema over the tiling of this scene
+        with its own patch size and ``overlap_padding``, taken on the device (``_ops.scene_minmax``; mask = band sum of scene x
+        non-zero) -- what ``dataset_maxmin`` returns whenever no valid sample is 0 and every band has a positive maximum.  Two
+        quirks of the reference's fold are NOT imitated: it treats a running minimum of exactly 0 as unset (so a valid 0 sample
+        can be lost as the minimum) and starts the maximum at 0 (so an all-negative band returns 0).  A tile without a valid
+        pixel is skipped; the reference raises on such a tile.  Float32 scenes: NaN samples are skipped, +-inf take part.
+        ``stats_count`` keeps the number of valid pixels."""
+        from . import _ops as ops
+        grid = TileGrid(self.grid.xsize, self.grid.ysize, self.grid.patch_size, overlap_padding)
+        lo_x, hi_x, lo_y, hi_y, self.stats_count = ops.scene_minmax(self.x, self.y, ops.scene_tile_table(grid, range(len(grid))),
+                                                                    sample_type=self.sample_type)
+        return ([[float(a), float(b)] for a, b in zip(lo_x, hi_x)], [[float(a), float(b)] for a, b in zip(lo_y, hi_y)])
 
     def statistics(self, overlap_padding=(0, 0)):
         """``(meanX, stdX, meanY, stdY)`` as float64 arrays: CommonFunc.Dataset_mean / Dataset_std over the tiling of this scene
@@ -421,8 +470,21 @@ class ResidentScene:
         """``(x, y, ref, valid)`` of the tiles ``items`` (indices or a tile table), all on the device: x, y as
         ``PairTileDataset.__getitem__`` returns them (normalised with ``stats`` when given) or, with ``raw=True``, as
         ``raw_item`` does (plain samples -- for ``Segmentor.forward_raw``); ``ref`` (None without a reference map) and the
-        ``valid`` window mask are (n,1,py,px)."""
+        ``valid`` window mask are (n,1,py,px).  A scene with an enhancer (``set_enhance``) is cut with it, like
+        ``PairTileDataset(enhance=)``."""
         from . import _ops as ops
+        if self.enhance_kind > 1 and not raw:
+            # SCALE / SCALE_NORM: the set cut has the modes -- a private one-scene set over the same tensors, same tiles
+            table = self.table(items)
+            if table.items is None:
+                raise ops._lib.FcdError('ResidentScene.cut: with SCALE / SCALE_NORM pass tile indices or a table made from them')
+            if self._solo is None:
+                self._solo = ResidentSceneSet([self])
+            x, y, ref, _, valid = ops.scene_set_cut(self._solo._descs, self._solo.table, self._solo.index(table.items), self.bands,
+                                                    self.sample_type, stats=self._solo._stats_dev, want_ref=self.ref is not None,
+                                                    want_region=False, mode=self.enhance_kind,
+                                                    scale=self.enhance_scale or (-1, 1))
+            return x, y, ref, valid
         return ops.scene_cut(self.x, self.y, self.table(items), ref=self.ref, stats=None if raw else self._stats_dev,
                              sample_type=self.sample_type, ref_type=self.ref_type if self.ref is not None else None)
 
@@ -473,6 +535,12 @@ def check_scene_set(scenes):
         got = [get(s) for s in scenes]
         if any(g != got[0] for g in got):
             raise ops._lib.FcdError('ResidentSceneSet: the scenes must share one %s, got %s' % (what, got))
+    # one enhancement mode per launch: the scenes that have an enhancer share its kind and, for SCALE_NORM, its range
+    # (scenes without one stay raw)
+    kinds = [(getattr(s, 'enhance_kind', 0), getattr(s, 'enhance_scale', None)) for s in scenes]
+    kinds = [k for k in kinds if k[0]]
+    if any(k != kinds[0] for k in kinds):
+        raise ops._lib.FcdError('ResidentSceneSet: the scenes must share one enhancer kind (and SCALE_NORM range), got %s' % (kinds,))
 
 
 class ResidentSceneSet:
@@ -483,10 +551,17 @@ class ResidentSceneSet:
     sample type, patch size and padding.  Statistics are read when the set is made: call :meth:`refresh` after
     ``ResidentScene.set_stats``."""
 
-    def __init__(self, scenes, names=None):
+    def __init__(self, scenes, names=None, transforms=None):
         from . import _ops as ops
         self.scenes = list(scenes)
         check_scene_set(self.scenes)
+        # ``transforms``: one eraser of ``transforms`` for every scene, or a list with one per scene (None entries allowed), as
+        # OSCD_Dataset_RSS takes them; used by :meth:`epoch` only (``cut`` erases what it is handed)
+        if transforms is not None and not isinstance(transforms, (list, tuple)):
+            transforms = [transforms] * len(self.scenes)
+        if transforms is not None and len(transforms) != len(self.scenes):
+            raise ValueError("The list of transforms doesn't match the file list")          # data_utils.py:354-356
+        self.transforms = None if transforms is None or all(t is None for t in transforms) else list(transforms)
         self.names = list(names) if names is not None else ['scene%d' % i for i in range(len(self.scenes))]
         self.numlist = [len(s) for s in self.scenes]
         self.cumlen = np.cumsum(np.array(self.numlist)).tolist()
@@ -501,6 +576,9 @@ class ResidentSceneSet:
     def refresh(self):
         """Rebuild the descriptor table and the statistics array from the scenes' current tensors and statistics."""
         C = self.bands
+        check_scene_set(self.scenes)
+        kinds = [(s.enhance_kind, s.enhance_scale) for s in self.scenes if s.enhance_kind]
+        self.mode, self.scale = (kinds[0][0], kinds[0][1] or (-1.0, 1.0)) if kinds else (1, (-1.0, 1.0))
         rows, stats = [], []
         for s in self.scenes:
             off = -1
@@ -540,14 +618,30 @@ class ResidentSceneSet:
         from . import _ops as ops
         return ops.DeviceRects(self.table, self.index(index), n)
 
-    def cut(self, items, raw=False, out=None, want_valid=True):
+    def erase_rects(self, regions, n):
+        """The validated rectangles (``_ops.EraseRects``) of ``n`` tiles from host regions, with as many slots per tile as the
+        set's erasers can draw (16 without erasers)."""
+        from . import _ops as ops
+        R = max(t.max_regions for t in self.transforms if t is not None) if self.transforms else ops.ERASE_MAX
+        return ops.erase_rects(regions, n, R, self.patch_size)
+
+    def cut(self, items, raw=False, out=None, want_valid=True, erase=None):
         """``(x, y, ref, region, valid)`` of the global ``items`` (a list, or the ``TileIndex`` :meth:`index` returns), all on the
         device: x, y, ref as ``MultiSceneDataset([RegionTileDataset...])[i]`` returns them (each tile normalised with its own
         scene's statistics; ``raw=True``: plain samples), ``region`` binarised like data_utils.py:280, ``valid`` the window
-        mask of ``raw_item``.  A scene without a reference / region map gives zero tiles."""
+        mask of ``raw_item``.  A scene without a reference / region map gives zero tiles.  The scenes' enhancer decides the
+        formula (NORMALIZE, SCALE or SCALE_NORM).  ``erase``: one region per item as the erasers of ``transforms`` return them
+        (or the ``EraseRects`` made from them), blanked in x and y alike; not with ``raw=True``."""
         from . import _ops as ops
-        return ops.scene_set_cut(self._descs, self.table, self.index(items), self.bands, self.sample_type,
-                                 stats=None if raw else self._stats_dev, want_valid=want_valid, out=out)
+        index = self.index(items)
+        if erase is not None:
+            if raw:
+                raise ValueError('cut: erasing has no raw route (erase after normalisation)')
+            if not isinstance(erase, ops.EraseRects):
+                erase = self.erase_rects(erase, len(index))
+        return ops.scene_set_cut(self._descs, self.table, index, self.bands, self.sample_type,
+                                 stats=None if raw else self._stats_dev, want_valid=want_valid, out=out, mode=self.mode,
+                                 scale=self.scale, erase=erase)
 
     def epoch(self, batch_size, seed, shuffle=True, ragged='pad', rank=None, world=None):
         """An iterable with ``demos._Epoch``'s contract, ``((x, y, item, ref[, region]), n_real, weight)`` -- ``region`` when a
@@ -569,13 +663,27 @@ class _ResidentEpoch:
         # slice of it -- inside the epoch there is no host-to-device copy and nothing that makes the host wait for the device
         plan = EpochPlan(*self.args)
         index = self.set.index(plan.flat) if plan.flat else None
-        return self._batches(plan, index)
+        return self._batches(plan, index, self._draw(plan))
 
-    def _batches(self, plan, index):
+    def _draw(self, plan):
+        """With erasers: the regions of every entry of the flat plan, drawn here in plan order -- padded duplicates included, as
+        the host loader fetches and draws them again -- each from its own scene's eraser, and uploaded ONCE next to the index."""
+        s = self.set
+        if s.transforms is None or not plan.flat:
+            return None
+        shape = (s.bands, s.patch_size[1], s.patch_size[0])
+        regions = []
+        for item in plan.flat:
+            t = s.transforms[s.locate(item)[0]]
+            regions.append(None if t is None else t.draw(shape))
+        return s.erase_rects(regions, len(plan.flat)).to(s.device)
+
+    def _batches(self, plan, index, rects=None):
         s = self.set
         for b, items in enumerate(plan.batches):
             part = index[plan.offsets[b]:plan.offsets[b + 1]]
-            x, y, ref, region, _ = s.cut(part, want_valid=False)
+            erase = None if rects is None else rects[plan.offsets[b]:plan.offsets[b + 1]]
+            x, y, ref, region, _ = s.cut(part, want_valid=False, erase=erase)
             real = len(items) - plan.pads[b]
             w = EpochWeight(real / float(plan.n))
             w.loss_scale = plan.scales[b]
@@ -669,6 +777,65 @@ def scene_meanstd(txt_x, txt_y, scene, overlap_padding=(0, 0)):
     mx, sx = _read_stats(txt_x)
     my, sy = _read_stats(txt_y)
     return mx, sx, my, sy
+
+
+def _fold_maxmin(dataset):
+    """The per-tile fold of CommonFunc.Dataset_maxmin (CommonFunc.py:298-324), quirks included: the running minimum counts as
+    unset while it is exactly 0, and the maximum starts at 0 (an all-negative band returns 0).  A tile without a valid pixel
+    raises, as the reference does (``torch.max`` of an empty selection)."""
+    a1 = a2 = None
+    for i in range(len(dataset)):
+        item = dataset[i]
+        x, y = item[0], item[1]
+        if a1 is None:
+            a1 = [[0.0, 0.0] for _ in range(x.size()[0])]
+            a2 = [[0.0, 0.0] for _ in range(y.size()[0])]
+        idx = _valid(x)
+        for a, t in ((a1, x), (a2, y)):
+            hi = torch.max(t[:, idx], dim=1)[0]
+            lo = torch.min(t[:, idx], dim=1)[0]
+            for b in range(t.size()[0]):
+                a[b][0] = float(lo[b]) if a[b][0] == 0 else a[b][0]
+                a[b][0] = float(lo[b]) if lo[b] < a[b][0] else a[b][0]
+                a[b][1] = float(hi[b]) if hi[b] > a[b][1] else a[b][1]
+    return a1, a2
+
+
+def _write_maxmin(path, ranges, fmt=str):
+    with open(path, 'w') as f:
+        f.write('max:' + ''.join(' {}'.format(fmt(r[1])) for r in ranges) + '\n')
+        f.write('min:' + ''.join(' {}'.format(fmt(r[0])) for r in ranges) + '\n')
+
+
+def _read_maxmin(path):
+    with open(path) as f:
+        lines = f.readlines()
+    hi, lo = [float(v) for v in lines[0].split()[1:]], [float(v) for v in lines[1].split()[1:]]
+    return [[lo[i], hi[i]] for i in range(len(hi))]
+
+
+def dataset_maxmin(txt1, txt2, dataset):
+    """Two lists of ``[min, max]`` per band, of scene x and of scene y, over the valid pixels of all patches of an UNENHANCED
+    tile dataset (CommonFunc.Dataset_maxmin, CommonFunc.py:294-370; the mask comes from the first scene), cached in the
+    reference's two text files (``max: v v ...`` / ``min: v v ...``): computed and written when either file is missing, read
+    back otherwise.  These are the ranges ``transforms.SCALE`` / ``SCALE_NORM`` take."""
+    if not (os.path.exists(txt1) and os.path.exists(txt2)):
+        a1, a2 = _fold_maxmin(dataset)
+        _write_maxmin(txt1, a1)
+        _write_maxmin(txt2, a2)
+        return a1, a2
+    return _read_maxmin(txt1), _read_maxmin(txt2)
+
+
+def scene_maxmin(txt1, txt2, scene, overlap_padding=(0, 0)):
+    """``dataset_maxmin`` for a ``ResidentScene``: the same two text files -- read back when both exist, else taken on the device
+    (``scene.maxmin``) and written with ``repr``, so reading them back is exact; files of either function load in the other."""
+    if not (os.path.exists(txt1) and os.path.exists(txt2)):
+        a1, a2 = scene.maxmin(overlap_padding)
+        _write_maxmin(txt1, a1, repr)
+        _write_maxmin(txt2, a2, repr)
+        return a1, a2
+    return _read_maxmin(txt1), _read_maxmin(txt2)
 
 
 def normalize_(x, mean, std):

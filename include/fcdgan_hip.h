@@ -486,6 +486,34 @@ int fcd_scene_set_cut(const fcd_scene_desc* descs, int S, int sample_type, int C
 size_t fcd_scene_stats_ws_bytes(int sample_type, int C, int n, int ph);
 int fcd_scene_stats(const void* scene_x, const void* scene_y, int sample_type, int C, int H, int W, const int32_t* table,
                     int n, int ph, int pw, void* out, void* ws, size_t ws_bytes, void* stream);
+/* The set cut with the reference's other pre-processing (CommonFunc.py:78-224): an enhancement mode for the whole launch and
+ * up to FCD_ERASE_MAX erased rectangles per tile.  Everything else is the set cut's, argument for argument.
+ *   mode: applied to the x and y planes of the scenes whose stats_off >= 0; stats then holds 4*C doubles per scene --
+ *     meanX, stdX, meanY, stdY (NORMALIZE) or loX, hiX, loY, hiY (SCALE, SCALE_NORM).  Per sample v, in fp64, then cast:
+ *       1  (v - mean) / std          2  (v - lo) / (hi - lo)          3  ((s1 - s0) * (v - lo)) / (hi - lo) + s0
+ *     with true divisions in that order: the result equals NumPy's float64 evaluation followed by astype(float32), bit for bit.
+ *     0, or stats == NULL: plain samples.
+ *   erase: device int32 (n, R, 4) = x, y, w, h in TILE coordinates, 16-byte aligned, 0 <= R <= FCD_ERASE_MAX, NULL exactly when R == 0; a slot
+ *     with w == 0 or h == 0 is empty.  The caller validates every rectangle against the tile (0 <= x, 0 <= y, x + w <= pw,
+ *     y + h <= ph).  An x or y sample inside any rectangle of its tile is stored as +0.0f (an assignment: NaN and inf too);
+ *     ref_tiles, region_tiles and valid are never erased, and no rectangle changes an address that is read or written. */
+#define FCD_ENHANCE_NONE 0
+#define FCD_ENHANCE_NORMALIZE 1
+#define FCD_ENHANCE_SCALE 2
+#define FCD_ENHANCE_SCALE_NORM 3
+#define FCD_ERASE_MAX 16
+int fcd_scene_set_cut_aug(const fcd_scene_desc* descs, int S, int sample_type, int C, const int32_t* table, int T,
+                          const int32_t* index, int n, int ph, int pw, const double* stats, int mode, double s0, double s1,
+                          const int32_t* erase, int R, float* x, float* y, float* ref_tiles, float* region_tiles, float* valid,
+                          void* stream);
+/* Masked per-band minimum and maximum of a resident scene pair over the read rectangles of a tile table
+ * (CommonFunc.Dataset_maxmin, CommonFunc.py:294-370) under the mask of fcd_scene_stats.  C <= 32.
+ * out: 4*C floats -- minX[C], maxX[C], minY[C], maxY[C], exact for all three sample types; count: the number of valid pixels
+ * (a pixel read by two tiles counts twice).  float32 scenes: a NaN sample is skipped, +inf and -inf take part; a band without
+ * a comparable sample returns +inf / -inf.  ws: fcd_scene_minmax_ws_bytes.  No atomics; out and count are written. */
+size_t fcd_scene_minmax_ws_bytes(int C, int n, int ph);
+int fcd_scene_minmax(const void* scene_x, const void* scene_y, int sample_type, int C, int H, int W, const int32_t* table,
+                     int n, int ph, int pw, float* out, unsigned long long* count, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- loss terms ------------------------------------------------------------
  * Masked per-sample sums -- the reconstruction terms of Loss.py:76-84 (L1) and
