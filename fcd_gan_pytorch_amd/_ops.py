@@ -1442,6 +1442,24 @@ SAMPLE_U8, SAMPLE_U16, SAMPLE_F32 = 0, 1, 2
 _SAMPLE_OF = {torch.uint8: SAMPLE_U8, torch.uint16: SAMPLE_U16, torch.float32: SAMPLE_F32}
 
 
+def _upload_device(device, what):
+    """Where a host table is uploaded to: a CUDA/ROCm ``torch.device`` with its index filled in (``cuda`` and ``cuda:N`` of the
+    current device are ONE cache key); ``what`` = 'the tile table goes', ..."""
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise _lib.FcdError('fcd_gan_pytorch_amd: %s to a CUDA/ROCm device, not %s (no CPU fallback)' % (what, device))
+    return device if device.index is not None else torch.device('cuda', torch.cuda.current_device())
+
+
+def _check_rects(rects, ph, pw):
+    """Host rectangles (r0, r1, c0, c1) as an int64 (n,4) array and whether every one lies inside the (ph,pw) tile."""
+    import numpy as np
+    rc = np.asarray(rects, dtype=np.int64).reshape(-1, 4)
+    ok = not ((rc < 0).any() or (rc[:, 1] > ph).any() or (rc[:, 3] > pw).any() or (rc[:, 0] > rc[:, 1]).any() or
+              (rc[:, 2] > rc[:, 3]).any())
+    return rc, ok
+
+
 class TileTable:
     """A validated tile table: ``rows`` = host int32 (n,12) array, row = ``TileGrid.slices(item)`` flattened (own x0,y0,w,h | read
     rx,ry,rw,rh | canvas wx,wy,ww,wh), ``geom`` = the (W, H, pw, ph, padx, pady) it was validated against and, after
@@ -1456,9 +1474,7 @@ class TileTable:
         return self.rows.shape[0]
 
     def to(self, device):
-        device = torch.device(device)
-        if device.type != 'cuda':
-            raise _lib.FcdError('fcd_gan_pytorch_amd: the tile table goes to a CUDA/ROCm device, not %s (no CPU fallback)' % device)
+        device = _upload_device(device, 'the tile table goes')
         if device not in self._dev:
             self._dev[device] = torch.from_numpy(self.rows).to(device)
         return self._dev[device]
@@ -1523,6 +1539,27 @@ def _table_for(table, W, H, pw=None, ph=None):
     return table
 
 
+def _scene_pair(fn_name, scene_x, scene_y, sample_type, one_device=False):
+    """The two resident scenes of one (C,H,W) shape and sample type (``one_device``: and device) -> ``(sx, sy, sample type
+    code, C, H, W)``."""
+    sx, st = _scene_tensor(scene_x, 'scene_x', sample_type)
+    sy, st_y = _scene_tensor(scene_y, 'scene_y', sample_type)
+    if sx.dim() != 3 or sx.shape != sy.shape or st != st_y or (one_device and sx.device != sy.device):
+        raise _lib.FcdError('%s: the two scenes must be (C,H,W) %stensors of one shape and sample type'
+                            % (fn_name, 'device ' if one_device else ''))
+    return (sx, sy, st) + tuple(sx.shape)
+
+
+def _cut_out(fn_name, out, shapes, names, wants, dev):
+    """The canvases a cut writes: new ones of ``shapes`` where ``wants`` says so, or the caller's ``out`` tuple, checked."""
+    if out is None:
+        return tuple(torch.empty(sh, dtype=torch.float32, device=dev) if w else None for sh, w in zip(shapes, wants))
+    for t, shape, name in zip(out, shapes, names):
+        if t is not None and (_dev(t, 'out ' + name) is not t or tuple(t.shape) != shape or t.device != dev):
+            raise _lib.FcdError('%s: out %s must be a contiguous %s float32 tensor on %s' % (fn_name, name, shape, dev))
+    return tuple(out)
+
+
 @torch.no_grad()
 def scene_cut(scene_x, scene_y, table, ref=None, stats=None, want_valid=True, sample_type=None, ref_type=None, out=None):
     """Cut the tiles of ``table`` out of the resident scene pair ``(C,H,W)`` (uint8 / uint16 / float32 samples; ``sample_type``
@@ -1531,11 +1568,7 @@ def scene_cut(scene_x, scene_y, table, ref=None, stats=None, want_valid=True, sa
     stdY): normalise like the host path, bit-identically; None: plain ``float(v)``.
     Returns ``(x, y, ref_tiles or None, valid or None)``: (n,C,ph,pw) / (n,1,ph,pw) float32, every element written (``out`` =
     such a tuple of preallocated contiguous tensors to write into; no memset is needed)."""
-    sx, st = _scene_tensor(scene_x, 'scene_x', sample_type)
-    sy, st_y = _scene_tensor(scene_y, 'scene_y', sample_type)
-    if sx.dim() != 3 or sx.shape != sy.shape or st != st_y:
-        raise _lib.FcdError('scene_cut: the two scenes must be (C,H,W) tensors of one shape and sample type')
-    C, H, W = sx.shape
+    sx, sy, st, C, H, W = _scene_pair('scene_cut', scene_x, scene_y, sample_type)
     table = _table_for(table, W, H)
     _, _, pw, ph, _, _ = table.geom
     n = len(table)
@@ -1550,19 +1583,10 @@ def scene_cut(scene_x, scene_y, table, ref=None, stats=None, want_valid=True, sa
             raise _lib.FcdError('scene_cut: stats must be a device float64 tensor of 4*C values (meanX, stdX, meanY, stdY)')
         s = stats.contiguous()
     dev = sx.device
-    if out is None:
-        x = torch.empty((n, C, ph, pw), dtype=torch.float32, device=dev)
-        y = torch.empty_like(x)
-        rtile = torch.empty((n, 1, ph, pw), dtype=torch.float32, device=dev) if r is not None else None
-        valid = torch.empty((n, 1, ph, pw), dtype=torch.float32, device=dev) if want_valid else None
-    else:
-        x, y, rtile, valid = out
-        for t, shape, name in ((x, (n, C, ph, pw), 'x'), (y, (n, C, ph, pw), 'y'), (rtile, (n, 1, ph, pw), 'ref tiles'),
-                               (valid, (n, 1, ph, pw), 'valid')):
-            if t is not None and (_dev(t, 'out ' + name) is not t or tuple(t.shape) != shape or t.device != dev):
-                raise _lib.FcdError('scene_cut: out %s must be a contiguous %s float32 tensor on %s' % (name, shape, dev))
-        if (rtile is None) != (r is None):
-            raise _lib.FcdError('scene_cut: reference map and out reference tiles go together')
+    x, y, rtile, valid = _cut_out('scene_cut', out, ((n, C, ph, pw), (n, C, ph, pw), (n, 1, ph, pw), (n, 1, ph, pw)),
+                                  ('x', 'y', 'ref tiles', 'valid'), (True, True, r is not None, want_valid), dev)
+    if (rtile is None) != (r is None):
+        raise _lib.FcdError('scene_cut: reference map and out reference tiles go together')
     check(lib.fcd_scene_cut(_p(sx), _p(sy), st, _p(r), rt, C, H, W, _p(table.to(dev)), n, ph, pw, _p(s), _p(x), _p(y), _p(rtile),
                             _p(valid), _stream()), 'fcd_scene_cut')
     return x, y, rtile, valid
@@ -1621,32 +1645,30 @@ def tile_confusion(cmap, ref_tiles, rects, counts, prob_thresh=0.5, gt_map=(0, 1
     if cmap.dim() != 4 or cmap.shape[1] != 1 or cmap.shape != ref_tiles.shape:
         raise _lib.FcdError('tile_confusion: cmap and reference tiles must both be (N,1,ph,pw)')
     N, _, ph, pw = cmap.shape
-    if isinstance(rects, DeviceRects):          # resident rectangles through a resident index list: no upload here
+    resident = isinstance(rects, DeviceRects)   # resident rectangles through a resident index list: no upload here
+    if resident:
         if rects.table.patch != (pw, ph):
             raise _lib.FcdError('tile_confusion: the rectangles were validated for patch %dx%d, the tiles are %dx%d'
                                 % (rects.table.patch + (pw, ph)))
-        if not 0 < rects.n <= N:
-            raise _lib.FcdError('tile_confusion: %d rectangles for %d tiles' % (rects.n, N))
-        counts = _counts_arg(counts, cmap.device)
-        if counts is None:
-            raise _lib.FcdError('tile_confusion: counts is required')
-        check(lib.fcd_tile_confusion_items(_p(cmap), _p(ref_tiles), _p(rects.table.to(cmap.device)[1]), len(rects.table),
-                                           _p(rects.index.on(cmap.device)), rects.n, ph, pw, float(prob_thresh), float(gt_map[0]),
-                                           float(gt_map[1]), float(pre_map[0]), float(pre_map[1]), _p(counts), _stream()),
-              'fcd_tile_confusion_items')
-        return counts
-    rc = np.asarray(rects, dtype=np.int64).reshape(-1, 4)
-    if not 0 < rc.shape[0] <= N:
-        raise _lib.FcdError('tile_confusion: %d rectangles for %d tiles' % (rc.shape[0], N))
-    if (rc < 0).any() or (rc[:, 1] > ph).any() or (rc[:, 3] > pw).any() or (rc[:, 0] > rc[:, 1]).any() or (rc[:, 2] > rc[:, 3]).any():
+        n, inside = rects.n, True               # checked against the tile when the table was made
+    else:
+        rc, inside = _check_rects(rects, ph, pw)
+        n = rc.shape[0]
+    if not 0 < n <= N:
+        raise _lib.FcdError('tile_confusion: %d rectangles for %d tiles' % (n, N))
+    if not inside:
         raise _lib.FcdError('tile_confusion: a rectangle leaves the (%d,%d) tile' % (ph, pw))
     counts = _counts_arg(counts, cmap.device)
     if counts is None:
         raise _lib.FcdError('tile_confusion: counts is required')
-    rd = torch.from_numpy(np.ascontiguousarray(rc.astype(np.int32))).to(cmap.device)
-    check(lib.fcd_tile_confusion(_p(cmap), _p(ref_tiles), _p(rd), rc.shape[0], ph, pw, float(prob_thresh), float(gt_map[0]),
-                                 float(gt_map[1]), float(pre_map[0]), float(pre_map[1]), _p(counts), _stream()),
-          'fcd_tile_confusion')
+    tail = (n, ph, pw, float(prob_thresh), float(gt_map[0]), float(gt_map[1]), float(pre_map[0]), float(pre_map[1]), _p(counts),
+            _stream())
+    if resident:
+        check(lib.fcd_tile_confusion_items(_p(cmap), _p(ref_tiles), _p(rects.table.to(cmap.device)[1]), len(rects.table),
+                                           _p(rects.index.on(cmap.device)), *tail), 'fcd_tile_confusion_items')
+    else:
+        rd = torch.from_numpy(np.ascontiguousarray(rc.astype(np.int32))).to(cmap.device)
+        check(lib.fcd_tile_confusion(_p(cmap), _p(ref_tiles), _p(rd), *tail), 'fcd_tile_confusion')
     return counts
 
 
@@ -1669,11 +1691,7 @@ def scene_stats(scene_x, scene_y, table, sample_type=None, out=None):
     from the device, turned into fp64 by exact rational arithmetic here.  float32: two fp64 passes on the device, reproducible
     bit for bit.  ``out``: the device buffer of 1 + 4*C raw totals (int64 for integer scenes, float64 for float32) to reuse."""
     import numpy as np
-    sx, st = _scene_tensor(scene_x, 'scene_x', sample_type)
-    sy, st_y = _scene_tensor(scene_y, 'scene_y', sample_type)
-    if sx.dim() != 3 or sx.shape != sy.shape or st != st_y:
-        raise _lib.FcdError('scene_stats: the two scenes must be (C,H,W) tensors of one shape and sample type')
-    C, H, W = sx.shape
+    sx, sy, st, C, H, W = _scene_pair('scene_stats', scene_x, scene_y, sample_type)
     table = _table_for(table, W, H)
     _, _, pw, ph, _, _ = table.geom
     n, dev = len(table), sx.device
@@ -1717,11 +1735,7 @@ def scene_minmax(scene_x, scene_y, table, sample_type=None):
     :func:`scene_stats` (band sum of scene x non-zero).  Float32 scenes: NaN samples are skipped, +-inf take part; a band without
     a comparable sample returns (+inf, -inf)."""
     import numpy as np
-    sx, st = _scene_tensor(scene_x, 'scene_x', sample_type)
-    sy, st_y = _scene_tensor(scene_y, 'scene_y', sample_type)
-    if sx.dim() != 3 or sx.shape != sy.shape or st != st_y:
-        raise _lib.FcdError('scene_minmax: the two scenes must be (C,H,W) tensors of one shape and sample type')
-    C, H, W = sx.shape
+    sx, sy, st, C, H, W = _scene_pair('scene_minmax', scene_x, scene_y, sample_type)
     table = _table_for(table, W, H)
     _, _, pw, ph, _, _ = table.geom
     n, dev = len(table), sx.device
@@ -1769,10 +1783,9 @@ class SceneSetTable:
         import numpy as np
         self.sizes, self.patch, self.pad = [(int(w), int(h)) for w, h in sizes], tuple(patch), tuple(pad)
         validate_set_rows(rows, self.sizes, self.patch[0], self.patch[1], self.pad[0], self.pad[1])
-        rc = np.asarray(rects, dtype=np.int64).reshape(-1, 4)
         pw, ph = self.patch
-        if rc.shape[0] != np.asarray(rows).shape[0] or (rc < 0).any() or (rc[:, 1] > ph).any() or (rc[:, 3] > pw).any() or \
-                (rc[:, 0] > rc[:, 1]).any() or (rc[:, 2] > rc[:, 3]).any():
+        rc, inside = _check_rects(rects, ph, pw)
+        if rc.shape[0] != np.asarray(rows).shape[0] or not inside:
             raise _lib.FcdError('scene set table: one rectangle per tile, inside the (%d,%d) tile' % (ph, pw))
         self.rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).astype(np.int32))
         self.rects = np.ascontiguousarray(rc.astype(np.int32))
@@ -1783,11 +1796,7 @@ class SceneSetTable:
 
     def to(self, device):
         """(tile table, rectangle table) on ``device``."""
-        device = torch.device(device)
-        if device.type != 'cuda':
-            raise _lib.FcdError('fcd_gan_pytorch_amd: the tile table goes to a CUDA/ROCm device, not %s (no CPU fallback)' % device)
-        if device.index is None:
-            device = torch.device('cuda', torch.cuda.current_device())
+        device = _upload_device(device, 'the tile table goes')
         if device not in self._dev:
             self._dev[device] = (torch.from_numpy(self.rows).to(device), torch.from_numpy(self.rects).to(device))
         return self._dev[device]
@@ -1820,9 +1829,7 @@ class TileIndex:
         a = np.asarray(items, dtype=np.int64).reshape(-1)
         if a.size == 0 or (a < 0).any() or (a >= size).any():
             raise _lib.FcdError('tile index: %d entries, all must lie in [0, %d)' % (a.size, size))
-        device = torch.device(device)
-        if device.type != 'cuda':
-            raise _lib.FcdError('fcd_gan_pytorch_amd: the tile index goes to a CUDA/ROCm device, not %s (no CPU fallback)' % device)
+        device = _upload_device(device, 'the tile index goes')
         self.size = int(size)
         self.dev = torch.from_numpy(a.astype(np.int32)).pin_memory().to(device, non_blocking=True)
 
@@ -1873,9 +1880,7 @@ class EraseRects:
         return self.rows.shape[0]
 
     def to(self, device):
-        device = torch.device(device)
-        if device.type != 'cuda':
-            raise _lib.FcdError('fcd_gan_pytorch_amd: the erase rectangles go to a CUDA/ROCm device, not %s (no CPU fallback)' % device)
+        device = _upload_device(device, 'the erase rectangles go')
         if self.dev is None and self.R > 0:
             self.dev = torch.from_numpy(self.rows).pin_memory().to(device, non_blocking=True)
         return self
@@ -1956,20 +1961,16 @@ def scene_set_cut(descs, table, index, C, sample_type, stats=None, want_ref=True
         s = stats.contiguous()
     n, (pw, ph) = len(index), table.patch
     shapes = ((n, C, ph, pw), (n, C, ph, pw), (n, 1, ph, pw), (n, 1, ph, pw), (n, 1, ph, pw))
-    if out is None:
-        wants = (True, True, want_ref, want_region, want_valid)
-        out = tuple(torch.empty(sh, dtype=torch.float32, device=dev) if w else None for sh, w in zip(shapes, wants))
-    else:
+    if out is not None:
         out = tuple(out)
         if len(out) != 5 or out[0] is None or out[1] is None:
             raise _lib.FcdError('scene_set_cut: out = (x, y, ref or None, region or None, valid or None)')
-        for t, shape, name in zip(out, shapes, ('x', 'y', 'ref tiles', 'region tiles', 'valid')):
-            if t is not None and (_dev(t, 'out ' + name) is not t or tuple(t.shape) != shape or t.device != dev):
-                raise _lib.FcdError('scene_set_cut: out %s must be a contiguous %s float32 tensor on %s' % (name, shape, dev))
-    x, y, rtile, region, valid = out
+    out = _cut_out('scene_set_cut', out, shapes, ('x', 'y', 'ref tiles', 'region tiles', 'valid'),
+                   (True, True, want_ref, want_region, want_valid), dev)
     tab, _ = table.to(dev)
     if mode not in (0, 1, 2, 3):
         raise _lib.FcdError('scene_set_cut: mode %r (0 none, 1 normalize, 2 scale, 3 scale_norm)' % (mode,))
+    fn, aug = 'fcd_scene_set_cut', ()
     if mode != 1 or erase is not None:
         e, R = None, 0
         if erase is not None:
@@ -1978,12 +1979,9 @@ def scene_set_cut(descs, table, index, C, sample_type, stats=None, want_ref=True
             e, R = erase.on(dev), erase.R
             if e is not None and not e.is_contiguous():
                 raise _lib.FcdError('scene_set_cut: the erase rectangles must be contiguous')
-        check(lib.fcd_scene_set_cut_aug(_p(descs), S, sample_type, C, _p(tab), len(table), _p(index.on(dev)), n, ph, pw, _p(s),
-                                        int(mode), float(scale[0]), float(scale[1]), _p(e), R, _p(x), _p(y), _p(rtile), _p(region),
-                                        _p(valid), _stream()), 'fcd_scene_set_cut_aug')
-        return out
-    check(lib.fcd_scene_set_cut(_p(descs), S, sample_type, C, _p(tab), len(table), _p(index.on(dev)), n, ph, pw, _p(s), _p(x), _p(y),
-                                _p(rtile), _p(region), _p(valid), _stream()), 'fcd_scene_set_cut')
+        fn, aug = 'fcd_scene_set_cut_aug', (int(mode), float(scale[0]), float(scale[1]), _p(e), R)
+    check(getattr(lib, fn)(_p(descs), S, sample_type, C, _p(tab), len(table), _p(index.on(dev)), n, ph, pw, _p(s), *aug,
+                           *(_p(t) for t in out), _stream()), fn)
     return out
 
 

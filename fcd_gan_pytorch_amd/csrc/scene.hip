@@ -45,6 +45,35 @@ __device__ __forceinline__ float load_sample(const void* __restrict__ base, long
 }
 
 // ---- cut -------------------------------------------------------------------------------------------------------
+// One plane of one tile at one canvas row, decoded -- all of it wave-uniform: where the samples come from (``src`` of sample type
+// ``type``, canvas column i reads element sbase + i), where the row goes, and what happens on the way.  fcd_scene_cut_kernel and
+// the plain fcd_scene_set_cut_kernel decode their planes into this and run cut_row; the _aug instantiation keeps a loop of its own.
+struct CutPlane {
+  const void* src;
+  int type;
+  float* dst;
+  bool live, norm, ones, region;                   // live: this canvas row holds scene samples (columns wx .. wx + ww)
+  double mean, den;
+  long long sbase;
+  int wx, ww;
+};
+
+__device__ __forceinline__ void cut_row(const CutPlane& p, int lane, int pw) {
+  for (int i = lane; i < pw; i += FCD_WAVE) {
+    float v = 0.f;
+    if (p.live && i >= p.wx && i < p.wx + p.ww) {
+      if (p.ones) {
+        v = 1.f;
+      } else {
+        v = load_sample(p.src, p.sbase + i, p.type);
+        if (p.norm) v = (float)(((double)v - p.mean) / p.den);
+        if (p.region && v > 125.f) v = 1.f;                  // data_utils.py:280
+      }
+    }
+    p.dst[i] = v;
+  }
+}
+
 // planes of one tile: C of x, C of y, [ref], [valid]; one wave per (tile, plane, canvas row).
 __global__ __launch_bounds__(kBlock) void fcd_scene_cut_kernel(
     const void* __restrict__ sx, const void* __restrict__ sy, int stype, const void* __restrict__ sref, int rtype, int C,
@@ -60,40 +89,27 @@ __global__ __launch_bounds__(kBlock) void fcd_scene_cut_kernel(
     const int q = (int)(pl - (unsigned)t * planes);
     const int32_t* __restrict__ row = table + t * T_COLS;
     const int rx = row[T_RX], ry = row[T_RY], wx = row[T_WX], wy = row[T_WY], ww = row[T_WW], wh = row[T_WH];
-    const bool in_rows = j >= wy && j < wy + wh;
     // which plane: source, sample type, destination, per-band statistics
-    const void* src;
-    float* dst;
-    int type = stype, c = 0;
-    bool norm = false, ones = false;
+    CutPlane p{};
+    p.type = stype; p.wx = wx; p.ww = ww; p.den = 1.0;
+    p.live = j >= wy && j < wy + wh;
+    int c = 0;
     if (q < C) {
-      src = sx; c = q; dst = x + ((t * C + c) * ph + j) * pw; norm = stats != nullptr;
+      p.src = sx; c = q; p.dst = x + ((t * C + c) * ph + j) * pw; p.norm = stats != nullptr;
     } else if (q < 2 * C) {
-      src = sy; c = q - C; dst = y + ((t * C + c) * ph + j) * pw; norm = stats != nullptr;
+      p.src = sy; c = q - C; p.dst = y + ((t * C + c) * ph + j) * pw; p.norm = stats != nullptr;
     } else if (ref_tiles && q == 2 * C) {
-      src = sref; type = rtype; dst = ref_tiles + (t * ph + j) * pw;
+      p.src = sref; p.type = rtype; p.dst = ref_tiles + (t * ph + j) * pw;
     } else {
-      src = nullptr; ones = true; dst = valid + (t * ph + j) * pw;
+      p.ones = true; p.dst = valid + (t * ph + j) * pw;
     }
-    double mean = 0.0, stdv = 1.0;
-    if (norm) {          // stats = meanX[C], stdX[C], meanY[C], stdY[C]
+    if (p.norm) {        // stats = meanX[C], stdX[C], meanY[C], stdY[C]
       const double* __restrict__ s = stats + (q < C ? 0 : 2 * C);
-      mean = s[c]; stdv = s[C + c];
+      p.mean = s[c]; p.den = s[C + c];
     }
     // first sample of the scene row this canvas row reads, shifted so that canvas column i reads element i
-    const long long sbase = ((long long)c * H + (ry + (j - wy))) * W + (rx - wx);
-    for (int i = lane; i < pw; i += FCD_WAVE) {
-      float v = 0.f;
-      if (in_rows && i >= wx && i < wx + ww) {
-        if (ones) {
-          v = 1.f;
-        } else {
-          v = load_sample(src, sbase + i, type);
-          if (norm) v = (float)(((double)v - mean) / stdv);
-        }
-      }
-      dst[i] = v;
-    }
+    p.sbase = ((long long)c * H + (ry + (j - wy))) * W + (rx - wx);
+    cut_row(p, lane, pw);
   }
 }
 
@@ -207,7 +223,18 @@ __global__ __launch_bounds__(kCountBlock) void fcd_tile_confusion_kernel(
 }
 
 static bool sample_type_ok(int t) { return t == FCD_SAMPLE_U8 || t == FCD_SAMPLE_U16 || t == FCD_SAMPLE_F32; }
+static double sample_bytes(int t) { return t == FCD_SAMPLE_U8 ? 1.0 : t == FCD_SAMPLE_U16 ? 2.0 : 4.0; }
 
+// What the three cut entry points launch over: units = n tiles x planes (C of x, C of y and ``maps`` further canvases), one per
+// (blockIdx.y, trip of the grid-stride loop) and counted in 32 bits by the kernels, and the bytes the profiler is told about.
+static int cut_work(const char* fn, int sample_type, int C, int maps, int n, int ph, int pw, long long* units, double* bytes) {
+  const int planes = 2 * C + maps;
+  *units = (long long)n * planes;
+  FCD_CHECK_ARG(*units <= INT32_MAX, "%s: %d tiles x %d planes exceed 2^31 - 1", fn, n, planes);
+  const long long rows = *units * ph;
+  *bytes = (double)rows * pw * 4.0 + 2.0 * n * C * ph * pw * sample_bytes(sample_type);
+  return FCD_OK;
+}
 
 extern "C" int fcd_scene_cut(const void* scene_x, const void* scene_y, int sample_type, const void* ref, int ref_type, int C,
                              int H, int W, const int32_t* table, int n, int ph, int pw, const double* stats, float* x,
@@ -217,12 +244,11 @@ extern "C" int fcd_scene_cut(const void* scene_x, const void* scene_y, int sampl
   FCD_CHECK_ARG(sample_type_ok(sample_type), "fcd_scene_cut: sample type %d (0 uint8, 1 uint16, 2 float32)", sample_type);
   FCD_CHECK_ARG((ref != nullptr) == (ref_tiles != nullptr), "fcd_scene_cut: reference map and reference tiles go together");
   FCD_CHECK_ARG(!ref || sample_type_ok(ref_type), "fcd_scene_cut: reference sample type %d", ref_type);
-  const int planes = 2 * C + (ref_tiles ? 1 : 0) + (valid ? 1 : 0);
-  const long long units = (long long)n * planes;
-  FCD_CHECK_ARG(units <= INT32_MAX, "fcd_scene_cut: %d tiles x %d planes exceed 2^31 - 1", n, planes);
-  const long long rows = units * ph;
-  const double in_bytes = sample_type == FCD_SAMPLE_U8 ? 1.0 : sample_type == FCD_SAMPLE_U16 ? 2.0 : 4.0;
-  FcdProfScope prof(FCD_K_MISC, (hipStream_t)stream, 0.0, (double)rows * pw * 4.0 + 2.0 * n * C * ph * pw * in_bytes);
+  long long units;
+  double bytes;
+  const int maps = (ref_tiles ? 1 : 0) + (valid ? 1 : 0);
+  if (const int err = cut_work("fcd_scene_cut", sample_type, C, maps, n, ph, pw, &units, &bytes)) return err;
+  FcdProfScope prof(FCD_K_MISC, (hipStream_t)stream, 0.0, bytes);
   hipLaunchKernelGGL(fcd_scene_cut_kernel, row_grid(ph, units), dim3(kBlock), 0, (hipStream_t)stream, scene_x, scene_y,
                      sample_type, ref, ref_type, C, (long long)H, (long long)W, table, (int)units, ph, pw, stats, x, y, ref_tiles,
                      valid);
@@ -246,31 +272,32 @@ extern "C" int fcd_scene_stitch(const float* cmap, const int32_t* table, int n, 
   return FCD_OK;
 }
 
+// both confusion entry points: ``index`` (with T > 0) picks rows of the rectangle table, nullptr takes rectangle t for tile t
+static int tile_confusion(const char* fn, const float* cmap, const float* ref_tiles, const int32_t* rects, int T,
+                          const int32_t* index, int n, int ph, int pw, const SceneCountArgs& a, unsigned long long* counts,
+                          void* stream) {
+  FCD_CHECK_ARG(cmap && ref_tiles && rects && counts && n > 0 && ph > 0 && pw > 0, "%s: bad arguments", fn);
+  const long long rows = (long long)n * ph;
+  FcdProfScope prof(FCD_K_MISC, (hipStream_t)stream, 0.0, (double)rows * pw * 8.0);
+  hipLaunchKernelGGL(fcd_tile_confusion_kernel, count_grid(ph, n), dim3(kCountBlock), 0, (hipStream_t)stream, cmap, ref_tiles,
+                     rects, index, T, n, ph, pw, a, counts);
+  FCD_LAUNCH_CHECK(fn);
+  return FCD_OK;
+}
+
 extern "C" int fcd_tile_confusion(const float* cmap, const float* ref_tiles, const int32_t* rects, int n, int ph, int pw,
                                   float thresh, float gt0, float gt1, float pre0, float pre1, unsigned long long* counts,
                                   void* stream) {
-  FCD_CHECK_ARG(cmap && ref_tiles && rects && counts && n > 0 && ph > 0 && pw > 0, "fcd_tile_confusion: bad arguments");
-  const long long rows = (long long)n * ph;
-  FcdProfScope prof(FCD_K_MISC, (hipStream_t)stream, 0.0, (double)rows * pw * 8.0);
-  const SceneCountArgs a{thresh, gt0, gt1, pre0, pre1};
-  hipLaunchKernelGGL(fcd_tile_confusion_kernel, count_grid(ph, n), dim3(kCountBlock), 0, (hipStream_t)stream, cmap, ref_tiles,
-                     rects, (const int32_t*)nullptr, 0, n, ph, pw, a, counts);
-  FCD_LAUNCH_CHECK("fcd_tile_confusion");
-  return FCD_OK;
+  return tile_confusion("fcd_tile_confusion", cmap, ref_tiles, rects, 0, nullptr, n, ph, pw, {thresh, gt0, gt1, pre0, pre1}, counts,
+                        stream);
 }
 
 extern "C" int fcd_tile_confusion_items(const float* cmap, const float* ref_tiles, const int32_t* rect_table, int T,
                                         const int32_t* index, int n, int ph, int pw, float thresh, float gt0, float gt1,
                                         float pre0, float pre1, unsigned long long* counts, void* stream) {
-  FCD_CHECK_ARG(cmap && ref_tiles && rect_table && index && counts && T > 0 && n > 0 && ph > 0 && pw > 0,
-                "fcd_tile_confusion_items: bad arguments");
-  const long long rows = (long long)n * ph;
-  FcdProfScope prof(FCD_K_MISC, (hipStream_t)stream, 0.0, (double)rows * pw * 8.0);
-  const SceneCountArgs a{thresh, gt0, gt1, pre0, pre1};
-  hipLaunchKernelGGL(fcd_tile_confusion_kernel, count_grid(ph, n), dim3(kCountBlock), 0, (hipStream_t)stream, cmap, ref_tiles,
-                     rect_table, index, T, n, ph, pw, a, counts);
-  FCD_LAUNCH_CHECK("fcd_tile_confusion_items");
-  return FCD_OK;
+  FCD_CHECK_ARG(index && T > 0, "fcd_tile_confusion_items: bad arguments");
+  return tile_confusion("fcd_tile_confusion_items", cmap, ref_tiles, rect_table, T, index, n, ph, pw,
+                        {thresh, gt0, gt1, pre0, pre1}, counts, stream);
 }
 
 // ==== the training feed: cut from a SET of resident scenes, statistics of a resident scene ===============================
@@ -291,7 +318,7 @@ enum { TS_SCENE = T_COLS, TS_COLS = T_COLS + 1 };
 //     16-byte load per lane, issued before the table decode, which it does not depend on); the row test y <= j < y + h is a
 //     ballot -- a bit per rectangle in a scalar register, wave-uniform -- and the lanes test x <= i < x + w for the set bits only,
 //     with x and w read out of lane r (v_readlane).  Both tests are differences, so no sum of a validated rectangle can overflow.
-// AUG = false is the kernel of fcd_scene_set_cut, instruction for instruction what it was before the template.
+// AUG = false is the kernel of fcd_scene_set_cut: it compiles without the modes and the rectangle test.
 struct SceneAugArgs {
   int mode, R;
   double s0, s1;
@@ -327,147 +354,138 @@ __global__ __launch_bounds__(kBlock) void fcd_scene_set_cut_kernel(
     const fcd_scene_desc* __restrict__ d = descs + (ok ? s : 0);
     const long long H = d->H, W = d->W;
     const int rx = row[T_RX], ry = row[T_RY], wx = row[T_WX], wy = row[T_WY], ww = row[T_WW], wh = row[T_WH];
-    const bool in_rows = ok && j >= wy && j < wy + wh;
-    const void* src = nullptr;
-    float* dst;
-    int type = stype, c = 0, k = q - 2 * C;
-    bool norm = false, ones = false, region = false;
+    CutPlane p{};
+    p.type = stype; p.wx = wx; p.ww = ww;
+    int c = 0, k = q - 2 * C;
     if (q < C) {
-      src = (const void*)d->x; c = q; dst = x + ((t * C + c) * ph + j) * pw; norm = stats != nullptr && d->stats_off >= 0;
+      p.src = (const void*)d->x; c = q; p.dst = x + ((t * C + c) * ph + j) * pw; p.norm = stats != nullptr && d->stats_off >= 0;
     } else if (q < 2 * C) {
-      src = (const void*)d->y; c = q - C; dst = y + ((t * C + c) * ph + j) * pw; norm = stats != nullptr && d->stats_off >= 0;
+      p.src = (const void*)d->y; c = q - C; p.dst = y + ((t * C + c) * ph + j) * pw; p.norm = stats != nullptr && d->stats_off >= 0;
     } else if (ref_tiles && k == 0) {
-      src = (const void*)d->ref; type = d->ref_type; dst = ref_tiles + (t * ph + j) * pw;
+      p.src = (const void*)d->ref; p.type = d->ref_type; p.dst = ref_tiles + (t * ph + j) * pw;
     } else if (region_tiles && k == (ref_tiles ? 1 : 0)) {
-      src = (const void*)d->region; type = d->region_type; region = true; dst = region_tiles + (t * ph + j) * pw;
+      p.src = (const void*)d->region; p.type = d->region_type; p.region = true; p.dst = region_tiles + (t * ph + j) * pw;
     } else {
-      ones = true; dst = valid + (t * ph + j) * pw;
+      p.ones = true; p.dst = valid + (t * ph + j) * pw;
     }
-    if (AUG && aug.mode == FCD_ENHANCE_NONE) norm = false;
-    double mean = 0.0, stdv = 1.0;
-    if (norm) {          // this scene's meanX[C], stdX[C], meanY[C], stdY[C] (AUG, modes 2 and 3: loX, hiX, loY, hiY)
+    if (AUG && aug.mode == FCD_ENHANCE_NONE) p.norm = false;
+    double stdv = 1.0;
+    if (p.norm) {        // this scene's meanX[C], stdX[C], meanY[C], stdY[C] (AUG, modes 2 and 3: loX, hiX, loY, hiY)
       const double* __restrict__ st = stats + d->stats_off + (q < C ? 0 : 2 * C);
-      mean = st[c]; stdv = st[C + c];
+      p.mean = st[c]; stdv = st[C + c];
     }
     // ONE division per sample whatever the mode (all of this is wave-uniform): the divisor is std, or hi - lo for the two scales;
     // SCALE_NORM multiplies the numerator by s1 - s0 first and adds s0 last
     const int mode = AUG ? aug.mode : FCD_ENHANCE_NORMALIZE;
     const bool to_range = AUG && mode == FCD_ENHANCE_SCALE_NORM;
-    const double den = mode == FCD_ENHANCE_NORMALIZE ? stdv : stdv - mean, width = AUG ? aug.s1 - aug.s0 : 0.0;
-    const bool live_plane = in_rows && (ones || src != nullptr);        // an absent map (address 0) gives zero tiles
-    const long long sbase = ((long long)c * H + (ry + (j - wy))) * W + (rx - wx);
-    for (int i = lane; i < pw; i += FCD_WAVE) {
-      float v = 0.f;
-      if (live_plane && i >= wx && i < wx + ww) {
-        if (ones) {
-          v = 1.f;
-        } else {
-          v = load_sample(src, sbase + i, type);
-          if (norm) {
-            double e = (double)v - mean;
-            if (to_range) e = width * e;
-            e = e / den;
-            if (to_range) e = e + aug.s0;
-            v = (float)e;
+    p.den = mode == FCD_ENHANCE_NORMALIZE ? stdv : stdv - p.mean;
+    const double width = AUG ? aug.s1 - aug.s0 : 0.0;
+    p.live = ok && j >= wy && j < wy + wh && (p.ones || p.src != nullptr);      // an absent map (address 0) gives zero tiles
+    p.sbase = ((long long)c * H + (ry + (j - wy))) * W + (rx - wx);
+    if constexpr (!AUG) {
+      cut_row(p, lane, pw);
+    } else {
+      // the row loop of cut_row with the range and the rectangles, kept apart: merged into cut_row this instantiation measured
+      // outside the spread of the separate loop (profiles/scene_refactor.md)
+      for (int i = lane; i < pw; i += FCD_WAVE) {
+        float v = 0.f;
+        if (p.live && i >= wx && i < wx + ww) {
+          if (p.ones) {
+            v = 1.f;
+          } else {
+            v = load_sample(p.src, p.sbase + i, p.type);
+            if (p.norm) {
+              double e = (double)v - p.mean;
+              if (to_range) e = width * e;
+              e = e / p.den;
+              if (to_range) e = e + aug.s0;
+              v = (float)e;
+            }
+            if (p.region && v > 125.f) v = 1.f;                // data_utils.py:280
           }
-          if (region && v > 125.f) v = 1.f;                  // data_utils.py:280
         }
-      }
-      if (AUG) {
         bool gone = false;
-        for (unsigned long long m = hit; m; m &= m - 1) {    // wave-uniform trip count
+        for (unsigned long long m = hit; m; m &= m - 1) {      // wave-uniform trip count
           const int r = __builtin_ctzll(m);
           const int ex = __builtin_amdgcn_readlane(rect.x, r), ew = __builtin_amdgcn_readlane(rect.z, r);
           gone = gone || (i >= ex && i - ex < ew);
         }
-        if (gone) v = 0.f;                                   // an assignment: NaN and inf become +0 too
+        if (gone) v = 0.f;                                     // an assignment: NaN and inf become +0 too
+        p.dst[i] = v;
       }
-      dst[i] = v;
     }
   }
+}
+
+// both set-cut entry points; the plain one passes empty SceneAugArgs to the AUG = false instantiation
+template <bool AUG>
+static int set_cut(const char* fn, const fcd_scene_desc* descs, int S, int sample_type, int C, const int32_t* table, int T,
+                   const int32_t* index, int n, int ph, int pw, const double* stats, const SceneAugArgs& aug, float* x, float* y,
+                   float* ref_tiles, float* region_tiles, float* valid, void* stream) {
+  FCD_CHECK_ARG(descs && table && index && x && y && S > 0 && C > 0 && T > 0 && n > 0 && ph > 0 && pw > 0, "%s: bad arguments", fn);
+  FCD_CHECK_ARG(sample_type_ok(sample_type), "%s: sample type %d (0 uint8, 1 uint16, 2 float32)", fn, sample_type);
+  if (AUG) {
+    FCD_CHECK_ARG(aug.mode >= FCD_ENHANCE_NONE && aug.mode <= FCD_ENHANCE_SCALE_NORM,
+                  "%s: enhancement mode %d (0 none, 1 normalize, 2 scale, 3 scale_norm)", fn, aug.mode);
+    FCD_CHECK_ARG(aug.R >= 0 && aug.R <= FCD_ERASE_MAX, "%s: %d rectangles per tile, at most %d", fn, aug.R, FCD_ERASE_MAX);
+    FCD_CHECK_ARG((aug.erase != nullptr) == (aug.R > 0), "%s: the rectangle list goes with R > 0 (R = %d)", fn, aug.R);
+    FCD_CHECK_ARG(((uintptr_t)aug.erase & 15) == 0, "%s: the rectangle list must be 16-byte aligned", fn);
+  }
+  long long units;
+  double bytes;
+  const int maps = (ref_tiles ? 1 : 0) + (region_tiles ? 1 : 0) + (valid ? 1 : 0);
+  if (const int err = cut_work(fn, sample_type, C, maps, n, ph, pw, &units, &bytes)) return err;
+  FcdProfScope prof(FCD_K_MISC, (hipStream_t)stream, 0.0, bytes);
+  hipLaunchKernelGGL(fcd_scene_set_cut_kernel<AUG>, row_grid(ph, units), dim3(kBlock), 0, (hipStream_t)stream, descs, S,
+                     sample_type, C, table, T, index, (int)units, ph, pw, stats, x, y, ref_tiles, region_tiles, valid, aug);
+  FCD_LAUNCH_CHECK(fn);
+  return FCD_OK;
 }
 
 extern "C" int fcd_scene_set_cut(const fcd_scene_desc* descs, int S, int sample_type, int C, const int32_t* table, int T,
                                  const int32_t* index, int n, int ph, int pw, const double* stats, float* x, float* y,
                                  float* ref_tiles, float* region_tiles, float* valid, void* stream) {
-  FCD_CHECK_ARG(descs && table && index && x && y && S > 0 && C > 0 && T > 0 && n > 0 && ph > 0 && pw > 0,
-                "fcd_scene_set_cut: bad arguments");
-  FCD_CHECK_ARG(sample_type_ok(sample_type), "fcd_scene_set_cut: sample type %d (0 uint8, 1 uint16, 2 float32)", sample_type);
-  const int planes = 2 * C + (ref_tiles ? 1 : 0) + (region_tiles ? 1 : 0) + (valid ? 1 : 0);
-  const long long units = (long long)n * planes;
-  FCD_CHECK_ARG(units <= INT32_MAX, "fcd_scene_set_cut: %d tiles x %d planes exceed 2^31 - 1", n, planes);
-  const long long rows = units * ph;
-  const double in_bytes = sample_type == FCD_SAMPLE_U8 ? 1.0 : sample_type == FCD_SAMPLE_U16 ? 2.0 : 4.0;
-  FcdProfScope prof(FCD_K_MISC, (hipStream_t)stream, 0.0, (double)rows * pw * 4.0 + 2.0 * n * C * ph * pw * in_bytes);
-  hipLaunchKernelGGL(fcd_scene_set_cut_kernel<false>, row_grid(ph, units), dim3(kBlock), 0, (hipStream_t)stream, descs, S,
-                     sample_type, C, table, T, index, (int)units, ph, pw, stats, x, y, ref_tiles, region_tiles, valid, SceneAugArgs{});
-  FCD_LAUNCH_CHECK("fcd_scene_set_cut");
-  return FCD_OK;
+  return set_cut<false>("fcd_scene_set_cut", descs, S, sample_type, C, table, T, index, n, ph, pw, stats, SceneAugArgs{}, x, y,
+                        ref_tiles, region_tiles, valid, stream);
 }
 
 extern "C" int fcd_scene_set_cut_aug(const fcd_scene_desc* descs, int S, int sample_type, int C, const int32_t* table, int T,
                                      const int32_t* index, int n, int ph, int pw, const double* stats, int mode, double s0,
                                      double s1, const int32_t* erase, int R, float* x, float* y, float* ref_tiles,
                                      float* region_tiles, float* valid, void* stream) {
-  FCD_CHECK_ARG(descs && table && index && x && y && S > 0 && C > 0 && T > 0 && n > 0 && ph > 0 && pw > 0,
-                "fcd_scene_set_cut_aug: bad arguments");
-  FCD_CHECK_ARG(sample_type_ok(sample_type), "fcd_scene_set_cut_aug: sample type %d (0 uint8, 1 uint16, 2 float32)", sample_type);
-  FCD_CHECK_ARG(mode >= FCD_ENHANCE_NONE && mode <= FCD_ENHANCE_SCALE_NORM,
-                "fcd_scene_set_cut_aug: enhancement mode %d (0 none, 1 normalize, 2 scale, 3 scale_norm)", mode);
-  FCD_CHECK_ARG(R >= 0 && R <= FCD_ERASE_MAX, "fcd_scene_set_cut_aug: %d rectangles per tile, at most %d", R, FCD_ERASE_MAX);
-  FCD_CHECK_ARG((erase != nullptr) == (R > 0), "fcd_scene_set_cut_aug: the rectangle list goes with R > 0 (R = %d)", R);
-  FCD_CHECK_ARG(((uintptr_t)erase & 15) == 0, "fcd_scene_set_cut_aug: the rectangle list must be 16-byte aligned");
-  const int planes = 2 * C + (ref_tiles ? 1 : 0) + (region_tiles ? 1 : 0) + (valid ? 1 : 0);
-  const long long units = (long long)n * planes;
-  FCD_CHECK_ARG(units <= INT32_MAX, "fcd_scene_set_cut_aug: %d tiles x %d planes exceed 2^31 - 1", n, planes);
-  const long long rows = units * ph;
-  const double in_bytes = sample_type == FCD_SAMPLE_U8 ? 1.0 : sample_type == FCD_SAMPLE_U16 ? 2.0 : 4.0;
-  FcdProfScope prof(FCD_K_MISC, (hipStream_t)stream, 0.0, (double)rows * pw * 4.0 + 2.0 * n * C * ph * pw * in_bytes);
-  hipLaunchKernelGGL(fcd_scene_set_cut_kernel<true>, row_grid(ph, units), dim3(kBlock), 0, (hipStream_t)stream, descs, S,
-                     sample_type, C, table, T, index, (int)units, ph, pw, stats, x, y, ref_tiles, region_tiles, valid,
-                     SceneAugArgs{mode, R, s0, s1, erase});
-  FCD_LAUNCH_CHECK("fcd_scene_set_cut_aug");
-  return FCD_OK;
+  return set_cut<true>("fcd_scene_set_cut_aug", descs, S, sample_type, C, table, T, index, n, ph, pw, stats,
+                       SceneAugArgs{mode, R, s0, s1, erase}, x, y, ref_tiles, region_tiles, valid, stream);
 }
 
-// ---- statistics ------------------------------------------------------------------------------------------------------
-// Masked per-band moments over the read rectangles of a tile table (CommonFunc.Dataset_mean / Dataset_std,
-// CommonFunc.py:436-500): a pixel counts when the fp32 band sum of scene x is non-zero (NaN != 0: counts), for both scenes,
-// once per tile that reads it.  One wave per (tile, row of the read rectangle): the mask of up to 64 x 64 columns is kept as
-// one bit per chunk in a 64-bit register per lane, then every band is read once more under it.  Lane totals -> wave total
-// (shuffles) -> the wave's OWN slots in LDS (plain adds, no atomics, in the fixed order of the wave's tiles) -> workgroup
-// total, summed over the waves in index order.
-//   MODE 0, uint8 / uint16: n, sum x[C], sum x^2[C], sum y[C], sum y^2[C] as exact unsigned 64-bit integers at every level; the
-//           workgroup totals go to the caller's totals by integer atomics (order-independent, so run-to-run identical).
-//   MODE 1, float32 pass 1: n, sum x[C], sum y[C] in fp64, one partial row per workgroup in the workspace.
-//   MODE 2, float32 pass 2: sum (x - mean)^2[C], sum (y - mean)^2[C] about the fp64 means of pass 1, partials likewise.
-// The partial rows are folded in index order by fcd_scene_stats_fold_kernel: no floating-point atomics anywhere, and the grid
-// depends on (n, ph) only, so two runs agree bit for bit.
+// ---- the masked scan of the statistics and the extrema -------------------------------------------------------------------
+// Both go over the read rectangles of a tile table under one mask: a pixel counts when the fp32 band sum of scene x is non-zero
+// (NaN != 0: counts), for both scenes, once per tile that reads it.  One wave per (tile, row of the read rectangle): the mask of
+// up to 64 x 64 columns is kept as one bit per chunk in a 64-bit register per lane, then every band is read once more under it.
 constexpr int kStatBands = 32;                                         // 16 waves x (1 + 4 * 32) slots x 8 B = 16.1 KB of LDS
 constexpr int kStatSegment = FCD_WAVE * 64;                            // columns one mask register per lane covers
 
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+// v combined over the wavefront by ``op(mine, other lane's)`` (xor butterfly: every lane ends with the result)
+template <typename T, typename OP>
+__device__ __forceinline__ T wave_reduce(T v, OP op) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
   return v;
 }
-template <typename T> __device__ __forceinline__ T wave_total(T v);
-template <> __device__ __forceinline__ unsigned long long wave_total(unsigned long long v) { return wave_sum_u64(v); }
-template <> __device__ __forceinline__ double wave_total(double v) { return wave_sum_d(v); }
+struct OpSum { __device__ unsigned long long operator()(unsigned long long v, unsigned long long u) const { return v + u; } };
+struct OpMin { __device__ float operator()(float v, float u) const { return u < v ? u : v; } };     // a NaN u never replaces v
+struct OpMax { __device__ float operator()(float v, float u) const { return u > v ? u : v; } };
+__device__ __forceinline__ unsigned long long wave_total(unsigned long long v) { return wave_reduce(v, OpSum()); }
+__device__ __forceinline__ double wave_total(double v) { return wave_sum_d(v); }
 
-template <int MODE>
-__global__ __launch_bounds__(kCountBlock) void fcd_scene_stats_kernel(
-    const void* __restrict__ sx, const void* __restrict__ sy, int stype, int C, long long H, long long W,
-    const int32_t* __restrict__ table, int n, const double* __restrict__ mean, void* __restrict__ out) {
-  typedef typename std::conditional<MODE == 0, unsigned long long, double>::type acc_t;
-  __shared__ acc_t part[kCountWaves][1 + 4 * kStatBands];
-  const int lane = threadIdx.x & (FCD_WAVE - 1);
-  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int j = wave_row<kCountWaves>();
-  const int slots = MODE == 0 ? 1 + 4 * C : MODE == 1 ? 1 + 2 * C : 2 * C;
-  for (int k = lane; k < slots; k += FCD_WAVE) part[w][k] = 0;
-  __syncthreads();
-  for (long long t = blockIdx.y; t < n; t += gridDim.y) {    // no early return: every wave reaches the barrier below
+// The walk, written once.  Per 4096-column segment of a row: ``count(n)`` on lane 0 with the wave's number of valid pixels, then
+// for every band c a default-constructed LANE that takes ``sample(l, c, vx, vy)`` for each valid column of this lane, in column
+// order, and ends in ``band(l, c)``, called by all 64 lanes (it reduces over the wave).  The callers say what they accumulate and
+// where they keep it; nothing here returns early, so every wave reaches the caller's barrier.
+template <typename LANE, typename COUNT, typename SAMPLE, typename BAND>
+__device__ __forceinline__ void masked_scan(const void* __restrict__ sx, const void* __restrict__ sy, int stype, int C, long long H,
+                                            long long W, const int32_t* __restrict__ table, int n, int lane, int j, COUNT count,
+                                            SAMPLE sample, BAND band) {
+  for (long long t = blockIdx.y; t < n; t += gridDim.y) {
     const int32_t* __restrict__ row = table + t * T_COLS;
     const int rx = row[T_RX], ry = row[T_RY], rw = row[T_RW], rh = row[T_RH];
     if (j >= rh) continue;                                    // wave-uniform
@@ -483,40 +501,102 @@ __global__ __launch_bounds__(kCountBlock) void fcd_scene_stats_kernel(
           if (s != 0.f) bits |= 1ull << k;
         }
       }
-      if (MODE != 2) {
-        const acc_t cnt = wave_total<acc_t>((acc_t)__popcll(bits));
-        if (lane == 0) part[w][0] += cnt;
-      }
+      const unsigned long long cnt = wave_total((unsigned long long)__popcll(bits));
+      if (lane == 0) count(cnt);
       for (int c = 0; c < C; ++c) {
-        acc_t a0 = 0, a1 = 0, b0 = 0, b1 = 0;
+        LANE l;
         const long long cbase = (long long)c * H * W + rbase;
         for (int k = 0; k < chunks; ++k) {
           if (!((bits >> k) & 1)) continue;
           const int i = seg + k * FCD_WAVE + lane;
-          const float vx = load_sample(sx, cbase + i, stype), vy = load_sample(sy, cbase + i, stype);
-          if (MODE == 0) {                                   // uint8 / uint16 samples: exact in float, exact back
-            const acc_t ux = (acc_t)(unsigned)vx, uy = (acc_t)(unsigned)vy;
-            a0 += ux; a1 += ux * ux; b0 += uy; b1 += uy * uy;
-          } else if (MODE == 1) {
-            a0 += (acc_t)vx; b0 += (acc_t)vy;
-          } else {
-            const double dx = (double)vx - mean[c], dy = (double)vy - mean[C + c];
-            a0 += (acc_t)(dx * dx); b0 += (acc_t)(dy * dy);
+          sample(l, c, load_sample(sx, cbase + i, stype), load_sample(sy, cbase + i, stype));
+        }
+        band(l, c);
+      }
+    }
+  }
+}
+
+// ---- statistics ------------------------------------------------------------------------------------------------------
+// Masked per-band moments (CommonFunc.Dataset_mean / Dataset_std, CommonFunc.py:436-500).  Lane totals -> wave total (shuffles)
+// -> the wave's OWN slots in LDS (plain adds, no atomics, in the fixed order of the wave's tiles) -> workgroup total, summed over
+// the waves in index order.
+//   MODE 0, uint8 / uint16: n, sum x[C], sum x^2[C], sum y[C], sum y^2[C] as exact unsigned 64-bit integers at every level; the
+//           workgroup totals go to the caller's totals by integer atomics (order-independent, so run-to-run identical).
+//   MODE 1, float32 pass 1: n, sum x[C], sum y[C] in fp64, one partial row per workgroup in the workspace.
+//   MODE 2, float32 pass 2: sum (x - mean)^2[C], sum (y - mean)^2[C] about the fp64 means of pass 1, partials likewise.
+// The partial rows are folded in index order by fcd_scene_stats_fold_kernel: no floating-point atomics anywhere, and the grid
+// depends on (n, ph) only, so two runs agree bit for bit.
+template <int MODE>
+__global__ __launch_bounds__(kCountBlock) void fcd_scene_stats_kernel(
+    const void* __restrict__ sx, const void* __restrict__ sy, int stype, int C, long long H, long long W,
+    const int32_t* __restrict__ table, int n, const double* __restrict__ mean, void* __restrict__ out) {
+  typedef typename std::conditional<MODE == 0, unsigned long long, double>::type acc_t;
+  __shared__ acc_t part[kCountWaves][1 + 4 * kStatBands];
+  const int lane = threadIdx.x & (FCD_WAVE - 1);
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int j = wave_row<kCountWaves>();
+  const int slots = MODE == 0 ? 1 + 4 * C : MODE == 1 ? 1 + 2 * C : 2 * C;
+  for (int k = lane; k < slots; k += FCD_WAVE) part[w][k] = 0;
+  __syncthreads();
+  if constexpr (MODE == 0) {
+    // the integer moments keep a walk of their own, the one masked_scan has: merged into it this instantiation measured outside
+    // the spread of the separate loop (profiles/scene_refactor.md)
+    for (long long t = blockIdx.y; t < n; t += gridDim.y) {  // no early return: every wave reaches the barrier below
+      const int32_t* __restrict__ row = table + t * T_COLS;
+      const int rx = row[T_RX], ry = row[T_RY], rw = row[T_RW], rh = row[T_RH];
+      if (j >= rh) continue;                                  // wave-uniform
+      const long long rbase = (long long)(ry + j) * W + rx;
+      for (int seg = 0; seg < rw; seg += kStatSegment) {
+        const int chunks = std::min(64, (rw - seg + FCD_WAVE - 1) / FCD_WAVE);
+        unsigned long long bits = 0;
+        for (int k = 0; k < chunks; ++k) {
+          const int i = seg + k * FCD_WAVE + lane;
+          if (i < rw) {
+            float s = 0.f;
+            for (int c = 0; c < C; ++c) s += load_sample(sx, (long long)c * H * W + rbase + i, stype);
+            if (s != 0.f) bits |= 1ull << k;
           }
         }
-        a0 = wave_total<acc_t>(a0); b0 = wave_total<acc_t>(b0);
-        if (MODE == 0) { a1 = wave_total<acc_t>(a1); b1 = wave_total<acc_t>(b1); }
-        if (lane == 0) {
-          if (MODE == 0) {
+        const acc_t cnt = wave_total((acc_t)__popcll(bits));
+        if (lane == 0) part[w][0] += cnt;
+        for (int c = 0; c < C; ++c) {
+          acc_t a0 = 0, a1 = 0, b0 = 0, b1 = 0;
+          const long long cbase = (long long)c * H * W + rbase;
+          for (int k = 0; k < chunks; ++k) {
+            if (!((bits >> k) & 1)) continue;
+            const int i = seg + k * FCD_WAVE + lane;
+            const float vx = load_sample(sx, cbase + i, stype), vy = load_sample(sy, cbase + i, stype);
+            const acc_t ux = (acc_t)(unsigned)vx, uy = (acc_t)(unsigned)vy;   // uint8 / uint16 samples: exact in float, exact back
+            a0 += ux; a1 += ux * ux; b0 += uy; b1 += uy * uy;
+          }
+          a0 = wave_total(a0); b0 = wave_total(b0); a1 = wave_total(a1); b1 = wave_total(b1);
+          if (lane == 0) {
             part[w][1 + c] += a0; part[w][1 + C + c] += a1; part[w][1 + 2 * C + c] += b0; part[w][1 + 3 * C + c] += b1;
-          } else if (MODE == 1) {
-            part[w][1 + c] += a0; part[w][1 + C + c] += b0;
-          } else {
-            part[w][c] += a0; part[w][C + c] += b0;
           }
         }
       }
     }
+  } else {
+    struct Lane {
+      double a0 = 0, b0 = 0;                                 // sums over x and over y
+    };
+    masked_scan<Lane>(
+        sx, sy, stype, C, H, W, table, n, lane, j,
+        [&](unsigned long long cnt) { if (MODE == 1) part[w][0] += (double)cnt; },    // a count is exact in fp64 too
+        [&](Lane& l, int c, float vx, float vy) {
+          if (MODE == 1) {
+            l.a0 += (double)vx; l.b0 += (double)vy;
+          } else {
+            const double dx = (double)vx - mean[c], dy = (double)vy - mean[C + c];
+            l.a0 += dx * dx; l.b0 += dy * dy;
+          }
+        },
+        [&](Lane& l, int c) {
+          const double a0 = wave_total(l.a0), b0 = wave_total(l.b0);
+          const int at = MODE == 1 ? 1 : 0;
+          if (lane == 0) { part[w][at + c] += a0; part[w][at + C + c] += b0; }
+        });
   }
   __syncthreads();
   if ((int)threadIdx.x < slots) {
@@ -562,7 +642,7 @@ extern "C" int fcd_scene_stats(const void* scene_x, const void* scene_y, int sam
   FCD_CHECK_ARG(C <= kStatBands, "fcd_scene_stats: %d bands, at most %d", C, kStatBands);
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid = count_grid(ph, n);
-  const double bytes = (double)n * ph * pw * (3.0 * C) * (sample_type == FCD_SAMPLE_U8 ? 1.0 : sample_type == FCD_SAMPLE_U16 ? 2.0 : 4.0);
+  const double bytes = (double)n * ph * pw * (3.0 * C) * sample_bytes(sample_type);
   if (sample_type != FCD_SAMPLE_F32) {
     const unsigned long long vmax = sample_type == FCD_SAMPLE_U8 ? 255ull : 65535ull;
     const unsigned long long pixels = (unsigned long long)n * (unsigned long long)ph * (unsigned long long)pw;
@@ -595,30 +675,12 @@ extern "C" int fcd_scene_stats(const void* scene_x, const void* scene_y, int sam
 
 // ---- extrema ---------------------------------------------------------------------------------------------------------
 // Masked per-band minimum and maximum of both scenes over the read rectangles of a tile table (CommonFunc.Dataset_maxmin,
-// CommonFunc.py:294-370), under the mask of the statistics: the fp32 band sum of scene x is non-zero.  The structure is the
-// statistics kernel's -- one wave per (tile, row), mask bits per 64 x 64-column segment, wave reduction (shuffles), the wave's OWN
-// slots in LDS, one partial row per workgroup -- with min / max in place of sums.  Every sample type goes through float: uint8 and
-// uint16 are exact there, so ONE kernel serves all three and there is no atomic of any kind; the partial rows (4*C floats and a
-// 64-bit count per workgroup) are folded by fcd_scene_minmax_fold_kernel.  A sample replaces the running extremum only when it
-// compares below / above it, so a NaN sample is skipped and +-inf take part; the running values start at +inf / -inf, which is what
-// a band without a single comparable sample returns.
-__device__ __forceinline__ float wave_min_f(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float u = __shfl_xor(v, o, 64);
-    v = u < v ? u : v;
-  }
-  return v;
-}
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float u = __shfl_xor(v, o, 64);
-    v = u > v ? u : v;
-  }
-  return v;
-}
-
+// CommonFunc.py:294-370): the masked scan with min / max in place of sums -- wave reduction (shuffles), the wave's OWN slots in
+// LDS, one partial row per workgroup.  Every sample type goes through float: uint8 and uint16 are exact there, so ONE kernel
+// serves all three and there is no atomic of any kind; the partial rows (4*C floats and a 64-bit count per workgroup) are folded
+// by fcd_scene_minmax_fold_kernel.  A sample replaces the running extremum only when it compares below / above it, so a NaN
+// sample is skipped and +-inf take part; the running values start at +inf / -inf, which is what a band without a single
+// comparable sample returns.
 __global__ __launch_bounds__(kCountBlock) void fcd_scene_minmax_kernel(
     const void* __restrict__ sx, const void* __restrict__ sy, int stype, int C, long long H, long long W,
     const int32_t* __restrict__ table, int n, float* __restrict__ part_out, unsigned long long* __restrict__ cnt_out) {
@@ -631,44 +693,23 @@ __global__ __launch_bounds__(kCountBlock) void fcd_scene_minmax_kernel(
   for (int k = lane; k < slots; k += FCD_WAVE) part[w][k] = ((k / C) & 1) ? -INFINITY : INFINITY;
   if (lane == 0) pcnt[w] = 0;
   __syncthreads();
-  for (long long t = blockIdx.y; t < n; t += gridDim.y) {    // no early return: every wave reaches the barrier below
-    const int32_t* __restrict__ row = table + t * T_COLS;
-    const int rx = row[T_RX], ry = row[T_RY], rw = row[T_RW], rh = row[T_RH];
-    if (j >= rh) continue;                                    // wave-uniform
-    const long long rbase = (long long)(ry + j) * W + rx;    // first sample of this row in band 0
-    for (int seg = 0; seg < rw; seg += kStatSegment) {
-      const int chunks = std::min(64, (rw - seg + FCD_WAVE - 1) / FCD_WAVE);
-      unsigned long long bits = 0;                           // bit k: column seg + 64 k + lane is valid
-      for (int k = 0; k < chunks; ++k) {
-        const int i = seg + k * FCD_WAVE + lane;
-        if (i < rw) {
-          float s = 0.f;
-          for (int c = 0; c < C; ++c) s += load_sample(sx, (long long)c * H * W + rbase + i, stype);
-          if (s != 0.f) bits |= 1ull << k;
-        }
-      }
-      const unsigned long long cnt = wave_sum_u64((unsigned long long)__popcll(bits));
-      if (lane == 0) pcnt[w] += cnt;
-      for (int c = 0; c < C; ++c) {
-        float x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
-        const long long cbase = (long long)c * H * W + rbase;
-        for (int k = 0; k < chunks; ++k) {
-          if (!((bits >> k) & 1)) continue;
-          const int i = seg + k * FCD_WAVE + lane;
-          const float vx = load_sample(sx, cbase + i, stype), vy = load_sample(sy, cbase + i, stype);
-          x0 = vx < x0 ? vx : x0; x1 = vx > x1 ? vx : x1;
-          y0 = vy < y0 ? vy : y0; y1 = vy > y1 ? vy : y1;
-        }
-        x0 = wave_min_f(x0); x1 = wave_max_f(x1); y0 = wave_min_f(y0); y1 = wave_max_f(y1);
+  const OpMin lo;
+  const OpMax hi;
+  struct Lane {
+    float x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
+  };
+  masked_scan<Lane>(
+      sx, sy, stype, C, H, W, table, n, lane, j, [&](unsigned long long cnt) { pcnt[w] += cnt; },
+      [&](Lane& l, int, float vx, float vy) {
+        l.x0 = lo(l.x0, vx); l.x1 = hi(l.x1, vx); l.y0 = lo(l.y0, vy); l.y1 = hi(l.y1, vy);
+      },
+      [&](Lane& l, int c) {
+        const float x0 = wave_reduce(l.x0, lo), x1 = wave_reduce(l.x1, hi), y0 = wave_reduce(l.y0, lo), y1 = wave_reduce(l.y1, hi);
         if (lane == 0) {
-          part[w][c] = x0 < part[w][c] ? x0 : part[w][c];
-          part[w][C + c] = x1 > part[w][C + c] ? x1 : part[w][C + c];
-          part[w][2 * C + c] = y0 < part[w][2 * C + c] ? y0 : part[w][2 * C + c];
-          part[w][3 * C + c] = y1 > part[w][3 * C + c] ? y1 : part[w][3 * C + c];
+          part[w][c] = lo(part[w][c], x0); part[w][C + c] = hi(part[w][C + c], x1);
+          part[w][2 * C + c] = lo(part[w][2 * C + c], y0); part[w][3 * C + c] = hi(part[w][3 * C + c], y1);
         }
-      }
-    }
-  }
+      });
   __syncthreads();
   const long long block = (long long)blockIdx.y * gridDim.x + blockIdx.x;
   if ((int)threadIdx.x < slots) {
@@ -676,7 +717,7 @@ __global__ __launch_bounds__(kCountBlock) void fcd_scene_minmax_kernel(
     float v = part[0][threadIdx.x];
     for (int k = 1; k < kCountWaves; ++k) {
       const float u = part[k][threadIdx.x];
-      v = is_max ? (u > v ? u : v) : (u < v ? u : v);
+      v = is_max ? hi(v, u) : lo(v, u);
     }
     part_out[block * slots + threadIdx.x] = v;
   } else if ((int)threadIdx.x == slots) {                    // slots <= 128 < the block size
@@ -699,14 +740,14 @@ __global__ __launch_bounds__(FCD_WAVE) void fcd_scene_minmax_fold_kernel(const f
     float v = is_max ? -INFINITY : INFINITY;
     for (int b = lane; b < blocks; b += FCD_WAVE) {
       const float u = partials[(long long)b * slots + k];
-      v = is_max ? (u > v ? u : v) : (u < v ? u : v);
+      v = is_max ? OpMax()(v, u) : OpMin()(v, u);
     }
-    v = is_max ? wave_max_f(v) : wave_min_f(v);
+    v = is_max ? wave_reduce(v, OpMax()) : wave_reduce(v, OpMin());
     if (lane == 0) out[k] = v;
   } else {
     unsigned long long s = 0;
     for (int b = lane; b < blocks; b += FCD_WAVE) s += counts[b];
-    s = wave_sum_u64(s);
+    s = wave_total(s);
     if (lane == 0) *count = s;
   }
 }
@@ -731,7 +772,7 @@ extern "C" int fcd_scene_minmax(const void* scene_x, const void* scene_y, int sa
   const int blocks = (int)(grid.x * grid.y);
   float* parts = (float*)ws;
   unsigned long long* counts = (unsigned long long*)((char*)ws + (size_t)blocks * 4 * C * sizeof(float));
-  const double bytes = (double)n * ph * pw * (3.0 * C) * (sample_type == FCD_SAMPLE_U8 ? 1.0 : sample_type == FCD_SAMPLE_U16 ? 2.0 : 4.0);
+  const double bytes = (double)n * ph * pw * (3.0 * C) * sample_bytes(sample_type);
   FcdProfScope prof(FCD_K_MISC, st, 0.0, bytes);
   hipLaunchKernelGGL(fcd_scene_minmax_kernel, grid, dim3(kCountBlock), 0, st, scene_x, scene_y, sample_type, C, (long long)H,
                      (long long)W, table, n, parts, counts);

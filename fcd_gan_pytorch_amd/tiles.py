@@ -221,6 +221,22 @@ def write_tiff(path, array, planar=True, rows_per_strip=None):
 
 
 # ------------------------------------------------------------------------ dataset
+def _load_scenes(scene_x, scene_y, ref=None, region=None, as_arrays=False):
+    """The scene pair and its optional (1,H,W) maps, each given as a (bands,H,W) array or as the path of a TIFF: read, and
+    checked to agree in size, with the reference's messages (data_utils.py:51,83,259).  ``as_arrays`` (the resident scene, which
+    uploads them): the scenes and the region map are made NumPy arrays, and the scenes must have three dimensions."""
+    def load(a, convert=as_arrays):
+        a = read_tiff(a) if isinstance(a, str) else a
+        return np.asarray(a) if convert and a is not None else a
+    scene_x, scene_y, ref, region = load(scene_x), load(scene_y), load(ref, False), load(region)
+    if scene_x.shape != scene_y.shape or (as_arrays and scene_x.ndim != 3):
+        raise ValueError("Image sizes don't match")
+    for m in (ref, region):
+        if m is not None and (m.shape[0] != 1 or m.shape[1:] != scene_x.shape[1:]):
+            raise ValueError("Reference sizes don't match image")
+    return scene_x, scene_y, ref, region
+
+
 class PairTileDataset(torch.utils.data.Dataset):
     """In-memory restatement of GDALDataset (data_utils.py:28-140): a bi-temporal scene pair
     (+ optional reference map) cut into overlapped patches.  ``__getitem__`` returns the
@@ -230,16 +246,7 @@ class PairTileDataset(torch.utils.data.Dataset):
                  stats=None, enhance=None, transforms=None):
         if stats is not None and enhance is not None:
             raise ValueError('PairTileDataset: give stats (NORMALIZE) or enhance, not both')
-        if isinstance(scene_x, str):
-            scene_x = read_tiff(scene_x)
-        if isinstance(scene_y, str):
-            scene_y = read_tiff(scene_y)
-        if isinstance(ref, str):
-            ref = read_tiff(ref)
-        if scene_x.shape != scene_y.shape:
-            raise ValueError("Image sizes don't match")
-        if ref is not None and (ref.shape[0] != 1 or ref.shape[1:] != scene_x.shape[1:]):
-            raise ValueError("Reference sizes don't match image")
+        scene_x, scene_y, ref, _ = _load_scenes(scene_x, scene_y, ref)
         self.x, self.y, self.ref = scene_x, scene_y, ref
         self.grid = TileGrid(scene_x.shape[2], scene_x.shape[1], patch_size, overlap_padding)
         self.stats = stats            # (meanX, stdX, meanY, stdY) per band, NORMALIZE semantics
@@ -331,41 +338,24 @@ class ResidentScene:
         from . import _ops as ops
         if stats is not None and enhance is not None:
             raise ValueError('ResidentScene: give stats (NORMALIZE) or enhance, not both')
-        if isinstance(scene_x, str):
-            scene_x = read_tiff(scene_x)
-        if isinstance(scene_y, str):
-            scene_y = read_tiff(scene_y)
-        if isinstance(ref, str):
-            ref = read_tiff(ref)
-        if isinstance(region, str):
-            region = read_tiff(region)
-        scene_x, scene_y = np.asarray(scene_x), np.asarray(scene_y)
-        if scene_x.shape != scene_y.shape or scene_x.ndim != 3:
-            raise ValueError("Image sizes don't match")
+        scene_x, scene_y, ref, region = _load_scenes(scene_x, scene_y, ref, region, as_arrays=True)
         if scene_x.dtype != scene_y.dtype or scene_x.dtype not in (np.uint8, np.uint16, np.float32):
             raise ops._lib.FcdError('ResidentScene: both scenes must be uint8, uint16 or float32 arrays of one type, got %s / %s'
                                     % (scene_x.dtype, scene_y.dtype))
-        if ref is not None and (ref.shape[0] != 1 or ref.shape[1:] != scene_x.shape[1:]):
-            raise ValueError("Reference sizes don't match image")
-        if region is not None:
-            region = np.asarray(region)
-            if region.shape[0] != 1 or region.shape[1:] != scene_x.shape[1:]:
-                raise ValueError("Reference sizes don't match image")
-            if region.dtype not in (np.uint8, np.uint16, np.float32):
-                raise ops._lib.FcdError('ResidentScene: the region map must be uint8, uint16 or float32, got %s' % region.dtype)
+        if region is not None and region.dtype not in (np.uint8, np.uint16, np.float32):
+            raise ops._lib.FcdError('ResidentScene: the region map must be uint8, uint16 or float32, got %s' % region.dtype)
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise ops._lib.FcdError('ResidentScene lives on a CUDA/ROCm device, not %s (no CPU fallback)' % self.device)
-        sample_type = {1: ops.SAMPLE_U8, 2: ops.SAMPLE_U16, 4: ops.SAMPLE_F32}[scene_x.dtype.itemsize]
+        sample_type = {1: ops.SAMPLE_U8, 2: ops.SAMPLE_U16, 4: ops.SAMPLE_F32}
 
         def up(a):          # uint16 samples travel as int16 bits (same bytes; the kernel reads them as uint16)
             a = np.ascontiguousarray(a)
             return torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(self.device)
-        self._attach(up(scene_x), up(scene_y), sample_type,
+        self._attach(up(scene_x), up(scene_y), sample_type[scene_x.dtype.itemsize],
                      None if ref is None else torch.from_numpy(np.ascontiguousarray(ref, dtype=np.float32)).to(self.device),
                      ops.SAMPLE_F32, None if region is None else up(region),
-                     0 if region is None else {1: ops.SAMPLE_U8, 2: ops.SAMPLE_U16, 4: ops.SAMPLE_F32}[region.dtype.itemsize],
-                     patch_size, overlap_padding, stats)
+                     0 if region is None else sample_type[region.dtype.itemsize], patch_size, overlap_padding, stats)
         if enhance is not None:
             self.set_enhance(enhance)
 
@@ -376,10 +366,7 @@ class ResidentScene:
         float32 samples (``sample_type=_ops.SAMPLE_U16`` for uint16 bits held in an int16 tensor), ``ref`` / ``region`` (1,H,W)
         likewise (``ref_type`` / ``region_type``).  The stitch kernel of ``infer_scene_resident`` wants a float32 ``ref``."""
         from . import _ops as ops
-        x, st = ops._scene_tensor(x, 'scene_x', sample_type)
-        y, st_y = ops._scene_tensor(y, 'scene_y', sample_type)
-        if x.dim() != 3 or x.shape != y.shape or st != st_y or x.device != y.device:
-            raise ops._lib.FcdError('ResidentScene: the two scenes must be (C,H,W) device tensors of one shape and sample type')
+        x, y, st, _, _, _ = ops._scene_pair('ResidentScene', x, y, sample_type, one_device=True)
         maps = []
         for t, typ, name in ((ref, ref_type, 'reference map'), (region, region_type, 'region map')):
             if t is None:
@@ -400,18 +387,22 @@ class ResidentScene:
         self.bands = int(x.shape[0])
         self.grid = TileGrid(int(x.shape[2]), int(x.shape[1]), patch_size, overlap_padding)
         self.stats, self._stats_dev, self.stats_count = None, None, None
-        self.enhance, self.enhance_kind, self.enhance_scale, self._solo = None, 0, None, None
+        self._clear_enhance()
         if isinstance(stats, str):
             if stats != 'auto':
                 raise ValueError("stats: (meanX, stdX, meanY, stdY), None or 'auto'")
             stats = self.statistics()
         self.set_stats(stats)
 
+    def _clear_enhance(self):
+        """No enhancer, and no private one-scene set made for one (``cut``)."""
+        self.enhance, self.enhance_kind, self.enhance_scale, self._solo = None, 0, None, None
+
     def set_stats(self, stats):
         """``stats`` = (meanX, stdX, meanY, stdY) per band, NORMALIZE semantics (as PairTileDataset), or None."""
         from . import _ops as ops
         self.stats, self._stats_dev = stats, None
-        self.enhance, self.enhance_kind, self.enhance_scale, self._solo = None, 0, None, None
+        self._clear_enhance()
         if stats is not None:
             s = np.stack([np.asarray(v, dtype=np.float64).reshape(-1) for v in stats])
             if s.shape != (4, self.bands):
@@ -440,11 +431,17 @@ class ResidentScene:
         can be lost as the minimum) and starts the maximum at 0 (so an all-negative band returns 0).  A tile without a valid
         pixel is skipped; the reference raises on such a tile.  Float32 scenes: NaN samples are skipped, +-inf take part.
         ``stats_count`` keeps the number of valid pixels."""
+        lo_x, hi_x, lo_y, hi_y = self._scan('scene_minmax', overlap_padding)
+        return ([[float(a), float(b)] for a, b in zip(lo_x, hi_x)], [[float(a), float(b)] for a, b in zip(lo_y, hi_y)])
+
+    def _scan(self, op, overlap_padding):
+        """``_ops.scene_stats`` / ``_ops.scene_minmax`` over the tiling of this scene with its own patch size and
+        ``overlap_padding``: the four per-band arrays; the valid-pixel count goes to ``stats_count``."""
         from . import _ops as ops
         grid = TileGrid(self.grid.xsize, self.grid.ysize, self.grid.patch_size, overlap_padding)
-        lo_x, hi_x, lo_y, hi_y, self.stats_count = ops.scene_minmax(self.x, self.y, ops.scene_tile_table(grid, range(len(grid))),
-                                                                    sample_type=self.sample_type)
-        return ([[float(a), float(b)] for a, b in zip(lo_x, hi_x)], [[float(a), float(b)] for a, b in zip(lo_y, hi_y)])
+        *out, self.stats_count = getattr(ops, op)(self.x, self.y, ops.scene_tile_table(grid, range(len(grid))),
+                                                  sample_type=self.sample_type)
+        return tuple(out)
 
     def statistics(self, overlap_padding=(0, 0)):
         """``(meanX, stdX, meanY, stdY)`` as float64 arrays: CommonFunc.Dataset_mean / Dataset_std over the tiling of this scene
@@ -453,11 +450,7 @@ class ResidentScene:
         fp64 evaluation (float32); the host functions round every tile mean to fp32, so the two routes agree to about seven
         digits.  Where the reference gives NaN (a tile without a valid pixel: mean of an empty selection times weight 0) this
         gives the finite statistic of the remaining tiles.  ``stats_count`` keeps the number of valid pixels."""
-        from . import _ops as ops
-        grid = TileGrid(self.grid.xsize, self.grid.ysize, self.grid.patch_size, overlap_padding)
-        mx, sx, my, sy, self.stats_count = ops.scene_stats(self.x, self.y, ops.scene_tile_table(grid, range(len(grid))),
-                                                           sample_type=self.sample_type)
-        return mx, sx, my, sy
+        return self._scan('scene_stats', overlap_padding)
 
     def __len__(self):
         return len(self.grid)
@@ -738,30 +731,35 @@ def dataset_std(dataset, mean_x, mean_y):
     return torch.sqrt(torch.sum(vx * w, dim=0)), torch.sqrt(torch.sum(vy * w, dim=0))
 
 
-def _write_stats(path, mean, std):
-    with open(path, 'w') as f:
-        f.write('mean:' + ''.join(' {}'.format(v) for v in mean) + '\n')
-        f.write('std:' + ''.join(' {}'.format(v) for v in std) + '\n')
-
-
-def _read_stats(path):
-    with open(path) as f:
-        lines = f.readlines()
-    return [float(v) for v in lines[0].split()[1:]], [float(v) for v in lines[1].split()[1:]]
+def _cached_rows(paths, labels, compute, fmt):
+    """The reference's text cache behind the four ``*_meanstd`` / ``*_maxmin`` functions: two files of two rows each,
+    ``label: v v ...``.  Both files there: read back, ``((row, row), (row, row))`` of float lists.  Else ``compute()`` returns
+    those rows of floats, which are written -- every value through ``fmt``: ``str``, or ``repr`` where the round trip must be
+    exact; either text loads here -- and returned."""
+    if not all(os.path.exists(p) for p in paths):
+        files = compute()
+        for path, rows in zip(paths, files):
+            with open(path, 'w') as f:
+                for label, row in zip(labels, rows):
+                    f.write(label + ':' + ''.join(' {}'.format(fmt(v)) for v in row) + '\n')
+        return files
+    files = []
+    for path in paths:
+        with open(path) as f:
+            lines = f.readlines()
+        files.append(([float(v) for v in lines[0].split()[1:]], [float(v) for v in lines[1].split()[1:]]))
+    return tuple(files)
 
 
 def dataset_meanstd(txt_x, txt_y, dataset):
     """``(meanX, stdX, meanY, stdY)`` as lists of floats, cached in two text files in the reference's
     format (``mean: v v ...`` / ``std: v v ...``; CommonFunc.Dataset_meanstd, CommonFunc.py:373-434):
     computed and written when either file is missing, read back otherwise."""
-    if not (os.path.exists(txt_x) and os.path.exists(txt_y)):
+    def compute():
         mx, my = dataset_mean(dataset)
         sx, sy = dataset_std(dataset, mx, my)
-        _write_stats(txt_x, mx, sx)
-        _write_stats(txt_y, my, sy)
-        return mx.numpy().tolist(), sx.numpy().tolist(), my.numpy().tolist(), sy.numpy().tolist()
-    mx, sx = _read_stats(txt_x)
-    my, sy = _read_stats(txt_y)
+        return (mx.numpy().tolist(), sx.numpy().tolist()), (my.numpy().tolist(), sy.numpy().tolist())
+    (mx, sx), (my, sy) = _cached_rows((txt_x, txt_y), ('mean', 'std'), compute, str)
     return mx, sx, my, sy
 
 
@@ -769,13 +767,10 @@ def scene_meanstd(txt_x, txt_y, scene, overlap_padding=(0, 0)):
     """``dataset_meanstd`` for a ``ResidentScene``: ``(meanX, stdX, meanY, stdY)`` as lists of floats, cached in the same two
     text files -- read back when both exist, else taken on the device (``scene.statistics``) and written.  The values are
     written with ``repr``, so reading them back is exact; files written by either function load in the other."""
-    if not (os.path.exists(txt_x) and os.path.exists(txt_y)):
+    def compute():
         mx, sx, my, sy = ([float(v) for v in a] for a in scene.statistics(overlap_padding))
-        _write_stats(txt_x, [repr(v) for v in mx], [repr(v) for v in sx])
-        _write_stats(txt_y, [repr(v) for v in my], [repr(v) for v in sy])
-        return mx, sx, my, sy
-    mx, sx = _read_stats(txt_x)
-    my, sy = _read_stats(txt_y)
+        return (mx, sx), (my, sy)
+    (mx, sx), (my, sy) = _cached_rows((txt_x, txt_y), ('mean', 'std'), compute, repr)
     return mx, sx, my, sy
 
 
@@ -801,17 +796,11 @@ def _fold_maxmin(dataset):
     return a1, a2
 
 
-def _write_maxmin(path, ranges, fmt=str):
-    with open(path, 'w') as f:
-        f.write('max:' + ''.join(' {}'.format(fmt(r[1])) for r in ranges) + '\n')
-        f.write('min:' + ''.join(' {}'.format(fmt(r[0])) for r in ranges) + '\n')
-
-
-def _read_maxmin(path):
-    with open(path) as f:
-        lines = f.readlines()
-    hi, lo = [float(v) for v in lines[0].split()[1:]], [float(v) for v in lines[1].split()[1:]]
-    return [[lo[i], hi[i]] for i in range(len(hi))]
+def _cached_maxmin(txt1, txt2, compute, fmt):
+    """``_cached_rows`` for two lists of ``[min, max]`` per band: the files hold a ``max:`` row above a ``min:`` row."""
+    files = _cached_rows((txt1, txt2), ('max', 'min'),
+                         lambda: tuple(([r[1] for r in a], [r[0] for r in a]) for a in compute()), fmt)
+    return tuple([[lo, hi] for hi, lo in zip(*rows)] for rows in files)
 
 
 def dataset_maxmin(txt1, txt2, dataset):
@@ -819,23 +808,13 @@ def dataset_maxmin(txt1, txt2, dataset):
     tile dataset (CommonFunc.Dataset_maxmin, CommonFunc.py:294-370; the mask comes from the first scene), cached in the
     reference's two text files (``max: v v ...`` / ``min: v v ...``): computed and written when either file is missing, read
     back otherwise.  These are the ranges ``transforms.SCALE`` / ``SCALE_NORM`` take."""
-    if not (os.path.exists(txt1) and os.path.exists(txt2)):
-        a1, a2 = _fold_maxmin(dataset)
-        _write_maxmin(txt1, a1)
-        _write_maxmin(txt2, a2)
-        return a1, a2
-    return _read_maxmin(txt1), _read_maxmin(txt2)
+    return _cached_maxmin(txt1, txt2, lambda: _fold_maxmin(dataset), str)
 
 
 def scene_maxmin(txt1, txt2, scene, overlap_padding=(0, 0)):
     """``dataset_maxmin`` for a ``ResidentScene``: the same two text files -- read back when both exist, else taken on the device
     (``scene.maxmin``) and written with ``repr``, so reading them back is exact; files of either function load in the other."""
-    if not (os.path.exists(txt1) and os.path.exists(txt2)):
-        a1, a2 = scene.maxmin(overlap_padding)
-        _write_maxmin(txt1, a1, repr)
-        _write_maxmin(txt2, a2, repr)
-        return a1, a2
-    return _read_maxmin(txt1), _read_maxmin(txt2)
+    return _cached_maxmin(txt1, txt2, lambda: scene.maxmin(overlap_padding), repr)
 
 
 def normalize_(x, mean, std):
