@@ -174,6 +174,10 @@ _SIGS = {
                                       P, P, P, P, P, P]),
     'fcd_scene_minmax_ws_bytes': (c_size_t, [c_int, c_int, c_int]),
     'fcd_scene_minmax': (c_int, [P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
+    'fcd_label_components_ws_bytes': (c_size_t, [c_int, c_int]),
+    'fcd_label_components': (c_int, [P, c_int, c_int, c_int, c_double, c_int, c_int, c_int, P, P, P, c_size_t, P]),
+    'fcd_component_boxes': (c_int, [P, c_int, c_int, c_int, P, P]),
+    'fcd_region_paint': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     'fcd_masked_recon_ws_bytes': (c_size_t, [c_int]),
     'fcd_masked_recon_fwd': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
     'fcd_masked_recon_bwd': (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),

@@ -1985,6 +1985,94 @@ def scene_set_cut(descs, table, index, C, sample_type, stats=None, want_ref=True
     return out
 
 
+# ------------------------------------------------------- region maps from a change map (csrc/regions.hip)
+def _slice_arg(fn_name, slice):
+    """``slice`` = None (one slice) or (slice_h, slice_w), both positive -> the C ABI's pair."""
+    if slice is None:
+        return 0, 0
+    sh, sw = (int(v) for v in slice)
+    if sh <= 0 or sw <= 0:
+        raise _lib.FcdError('%s: slice = (slice_h, slice_w), both positive, or None; got %r' % (fn_name, slice))
+    return sh, sw
+
+
+def _plane_shape(fn_name, H, W):
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0 or H * W > 2 ** 31 - 1:
+        raise _lib.FcdError('%s: %d x %d pixels; both positive and at most 2^31 - 1 in all' % (fn_name, H, W))
+    return H, W
+
+
+@torch.no_grad()
+def label_components(map, thresh, sample_type=None, connectivity=2, slice=None):
+    """``(labels, K)``: the connected components of ``double(map) > thresh`` (a NaN is background) of a resident (H,W) or
+    (1,H,W) plane of uint8 / uint16 / float32 samples (``sample_type=SAMPLE_U16`` for uint16 bits held in an int16 tensor).
+    ``connectivity`` 2 = 8 neighbours (``measure.label(connectivity=2)``, OSCDProcess.py:59), 1 = 4 neighbours; ``slice`` =
+    (slice_h, slice_w) cuts connectivity at slice borders (BuildingProcess.py:99-131 on the unsliced scene).  ``labels`` is int32
+    (H,W) on the device: 0 = background, 1..K in raster order of each component's first pixel (``scipy.ndimage.label``'s
+    numbering).  Reading K is the one host synchronisation: a set-up step, not for the training loop."""
+    m, st = _scene_tensor(map, 'change map', sample_type)
+    if m.dim() == 3 and m.shape[0] == 1:
+        m = m[0]
+    if m.dim() != 2:
+        raise _lib.FcdError('label_components: the map must be (H,W) or (1,H,W), got %s' % (tuple(map.shape),))
+    H, W = _plane_shape('label_components', *m.shape)
+    if connectivity not in (1, 2):
+        raise _lib.FcdError('label_components: connectivity %r (1: 4 neighbours, 2: 8 neighbours)' % (connectivity,))
+    sh, sw = _slice_arg('label_components', slice)
+    dev = m.device
+    labels = torch.empty((H, W), dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    nbytes = lib.fcd_label_components_ws_bytes(H, W)
+    ws = _ws(nbytes, dev)
+    check(lib.fcd_label_components(_p(m), st, H, W, float(thresh), int(connectivity), sh, sw, _p(labels), _p(count), _p(ws), nbytes,
+                                   _stream()), 'fcd_label_components')
+    return labels, int(count.item())
+
+
+@torch.no_grad()
+def component_boxes(labels, K):
+    """int32 (K,4) on the device: ``min_y, min_x, max_y, max_x`` of labels 1..K of an int32 (H,W) label image, half-open like
+    ``regionprops.bbox`` (OSCDProcess.py:63-66); row k is label k + 1."""
+    if not torch.is_tensor(labels) or not labels.is_cuda:
+        raise _lib.FcdError('fcd_gan_pytorch_amd: labels is on %s; the HIP path needs a CUDA/ROCm tensor (no CPU fallback)'
+                            % (labels.device if torch.is_tensor(labels) else type(labels).__name__))
+    if labels.dtype != torch.int32 or labels.dim() != 2 or not labels.is_contiguous():
+        raise _lib.FcdError('component_boxes: labels must be a contiguous int32 (H,W) tensor')
+    H, W = _plane_shape('component_boxes', *labels.shape)
+    K = int(K)
+    if K < 0 or K > H * W:
+        raise _lib.FcdError('component_boxes: %d components in %d x %d pixels' % (K, H, W))
+    boxes = torch.empty((K, 4), dtype=torch.int32, device=labels.device)
+    check(lib.fcd_component_boxes(_p(labels), H, W, K, _p(boxes) if K else None, _stream()), 'fcd_component_boxes')
+    return boxes
+
+
+@torch.no_grad()
+def region_paint(boxes, H, W, expand, slice=None, out=None):
+    """uint8 (H,W) on the device: 255 inside any of the (K,4) ``boxes`` grown by ``expand`` pixels and clamped like the reference
+    (OSCDProcess.py:68-73; with ``slice`` against the box's own slice, BuildingProcess.py:140-145), 0 elsewhere.  Every element
+    is written; ``out``: the map to reuse."""
+    if not torch.is_tensor(boxes) or not boxes.is_cuda:
+        raise _lib.FcdError('fcd_gan_pytorch_amd: boxes is on %s; the HIP path needs a CUDA/ROCm tensor (no CPU fallback)'
+                            % (boxes.device if torch.is_tensor(boxes) else type(boxes).__name__))
+    if boxes.dtype != torch.int32 or boxes.dim() != 2 or boxes.shape[1] != 4 or not boxes.is_contiguous():
+        raise _lib.FcdError('region_paint: boxes must be a contiguous int32 (K,4) tensor')
+    H, W = _plane_shape('region_paint', H, W)
+    expand = int(expand)
+    if expand < 0 or expand > 2 ** 31 - 1:
+        raise _lib.FcdError('region_paint: expand %d; not negative, below 2^31' % expand)
+    sh, sw = _slice_arg('region_paint', slice)
+    K = int(boxes.shape[0])
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.uint8, device=boxes.device)
+    elif not torch.is_tensor(out) or out.device != boxes.device or out.dtype != torch.uint8 or out.numel() != H * W or \
+            not out.is_contiguous():
+        raise _lib.FcdError('region_paint: out must be a contiguous uint8 tensor of %d x %d elements on %s' % (H, W, boxes.device))
+    check(lib.fcd_region_paint(_p(boxes) if K else None, K, H, W, expand, sh, sw, _p(out), _stream()), 'fcd_region_paint')
+    return out
+
+
 # ------------------------------------------------------------------------ losses
 class _MaskedSums(torch.autograd.Function):
     """out[2N] = {num[n], wsum[n]} of include/fcdgan_hip.h:fcd_masked_recon_fwd."""

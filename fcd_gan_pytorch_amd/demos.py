@@ -307,7 +307,8 @@ def _valid_centres(dataset, like, items, real):
 def demo_rsss(dataset, device='cuda', n_channels=4, epochs_g=50, epochs_adv=100, init_batch_size=20, batch_size=12,
               learning_rate=5e-5, perception_weight=0.1, ssim_weight=0, perception_perBand=True, l1_weight=0.02,
               g_weight=0.5, d_weight=1, r_weight=2, prob_thresh=0.5, gt_map=(1, 2), pre_map=(0, 1), seed=0,
-              netG_state=None, log=None, allow_seeded=False, load_g=None, save_s=None, save_g=None, save_d=None, ragged='pad'):
+              netG_state=None, log=None, allow_seeded=False, load_g=None, save_s=None, save_g=None, save_d=None, ragged='pad',
+              region_from_ref=None):
     """Demo_RSSS.py:27-538 on a ``datasets.MultiSceneDataset`` / ``RegionTileDataset`` (tuples
     ``(x, y, item, ref, region)``): G pre-training on the region-masked reconstruction (skipped when a
     generator checkpoint is given -- ``load_g``: path of a ``GModel.pkl`` as the reference writes it,
@@ -316,10 +317,18 @@ def demo_rsss(dataset, device='cuda', n_channels=4, epochs_g=50, epochs_adv=100,
     (``save_s/save_g/save_d``, Demo_RSSS.py:507-514).  Batch sizes are per rank under data parallelism.
     ``dataset`` may be a ``tiles.ResidentSceneSet`` (scenes with region maps, resident on the device): the same batches are
     then cut on the device (``ResidentSceneSet.epoch``) and the accuracy is one ``Evaluator.add_tiles`` call per batch on
-    resident rectangles -- no host work per tile, no copy per batch."""
+    resident rectangles -- no host work per tile, no copy per batch.  ``region_from_ref=(thresh, expand)``: a resident scene that
+    has a reference map but no region map gets one derived from it on the device (``ResidentScene.derive_region``: what
+    OSCDProcess.py:56-73 prepares offline; OSCD's recipe is ``(1, 10)``); the default None keeps the error."""
     dev = torch.device(device)
     resident = isinstance(dataset, tiles.ResidentSceneSet)
     if resident:
+        if region_from_ref is not None:
+            todo = [s for s in dataset.scenes if s.region is None and s.ref is not None]
+            for s in todo:
+                s.derive_region(region_from_ref[0], region_from_ref[1])
+            if todo:
+                dataset.refresh()
         if not dataset.has_region:
             raise ValueError('demo_rsss needs region maps: ResidentScene(..., region=...)')
         epoch = lambda bs, sd: dataset.epoch(bs, sd, ragged=ragged)

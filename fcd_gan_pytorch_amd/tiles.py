@@ -220,6 +220,190 @@ def write_tiff(path, array, planar=True, rows_per_strip=None):
             f.write(p)
 
 
+# ------------------------------------------------------- region maps from a change map
+# The reference prepares its regional supervision offline (OSCDProcess.py:56-73, BuildingProcess.py:127-145,167): threshold the
+# change map, ``skimage.measure.label(connectivity=2)``, ``regionprops`` boxes, every box grown by ``region_expand = 10`` pixels,
+# clamped and filled with 255 -- per 200x200 slice for the sliced WHU set, with one changed / unchanged flag per slice in
+# label.txt.  ``region_map`` does it on the device (csrc/regions.hip), ``region_map_host`` restates it in NumPy.
+# ``slice`` = (slice_h, slice_w) everywhere.  Recipes: OSCD ``thresh=1``, WHU ``thresh=0, slice=(200, 200)``.
+def _plane(ref):
+    """A change map given as (H,W) or (1,H,W) -> the (H,W) plane."""
+    a = np.asarray(ref)
+    if a.ndim == 3 and a.shape[0] == 1:
+        a = a[0]
+    if a.ndim != 2 or a.size == 0:
+        raise ValueError('the change map must be (H,W) or (1,H,W), got shape %s' % (np.asarray(ref).shape,))
+    return a
+
+
+def _slice_pair(slice):
+    if slice is None:
+        return None
+    sh, sw = (int(v) for v in slice)
+    if sh <= 0 or sw <= 0:
+        raise ValueError('slice = (slice_h, slice_w), both positive, or None; got %r' % (slice,))
+    return sh, sw
+
+
+def label_components_host(fg, connectivity=2, slice=None):
+    """``(labels int32 (H,W), K)`` of a boolean plane, numbered in raster order of each component's first pixel
+    (``scipy.ndimage.label``'s numbering), with connectivity cut at the borders of ``slice``.  Row runs by NumPy, a union-find over
+    the runs in plain Python: the oracle of ``_ops.label_components``, no scipy or skimage."""
+    fg = np.asarray(fg, dtype=bool)
+    H, W = fg.shape
+    if connectivity not in (1, 2):
+        raise ValueError('connectivity %r (1: 4 neighbours, 2: 8 neighbours)' % (connectivity,))
+    sl = _slice_pair(slice)
+    link = np.zeros((H, W), dtype=bool)                  # pixel continues the run of its left neighbour
+    link[:, 1:] = fg[:, 1:] & fg[:, :-1]
+    if sl:
+        link[:, ::sl[1]] = False
+    starts = fg & ~link
+    ends = fg.copy()
+    ends[:, :-1] &= ~link[:, 1:]
+    ry, rx0 = np.nonzero(starts)
+    rx1 = np.nonzero(ends)[1] + 1                        # same raster order: the k-th end closes the k-th start
+    n = len(ry)
+    parent = list(range(n))
+
+    def find(i):
+        while parent[i] != i:
+            parent[i] = parent[parent[i]]
+            i = parent[i]
+        return i
+    first = np.searchsorted(ry, np.arange(H + 1))        # runs of row y: first[y] .. first[y + 1]
+    reach = 1 if connectivity == 2 else 0                # a diagonal touch: the upper run ends where this one starts
+    x0, x1 = rx0.tolist(), rx1.tolist()
+    col = (rx0 // sl[1]).tolist() if sl else None
+    for y in range(1, H):
+        if sl and y % sl[0] == 0:
+            continue
+        a, a_end, b, b_end = int(first[y]), int(first[y + 1]), int(first[y - 1]), int(first[y])
+        while a < a_end and b < b_end:
+            if x0[a] < x1[b] + reach and x0[b] < x1[a] + reach and (col is None or col[a] == col[b]):
+                ra, rb = find(a), find(b)
+                if ra != rb:
+                    parent[max(ra, rb)] = min(ra, rb)
+            if x1[b] <= x1[a]:                           # the run that ends first cannot touch anything further right
+                b += 1
+            else:
+                a += 1
+    root = np.array([find(i) for i in range(n)], dtype=np.int64)
+    is_root = root == np.arange(n)
+    rank = np.cumsum(is_root)                            # runs are in raster order, a root is its component's first run
+    lab = rank[root] if n else root
+    flat = np.zeros(H * W + 1, dtype=np.int64)
+    np.add.at(flat, ry * W + rx0, lab)
+    np.add.at(flat, ry * W + rx1, -lab)
+    return np.cumsum(flat[:-1]).reshape(H, W).astype(np.int32), int(is_root.sum())
+
+
+def component_boxes_host(labels, K):
+    """int32 (K,4) ``min_y, min_x, max_y, max_x`` (half-open, ``regionprops.bbox``) of labels 1..K."""
+    labels = np.asarray(labels)
+    boxes = np.empty((K, 4), dtype=np.int64)
+    boxes[:, :2] = max(labels.shape)
+    boxes[:, 2:] = 0
+    y, x = np.nonzero(labels)
+    k = labels[y, x].astype(np.int64) - 1
+    np.minimum.at(boxes[:, 0], k, y)
+    np.minimum.at(boxes[:, 1], k, x)
+    np.maximum.at(boxes[:, 2], k, y + 1)
+    np.maximum.at(boxes[:, 3], k, x + 1)
+    return boxes.astype(np.int32)
+
+
+def region_paint_host(boxes, H, W, expand, slice=None):
+    """uint8 (H,W): 255 inside every box grown by ``expand`` and clamped with the reference's rule (OSCDProcess.py:68-73), against
+    the scene or, with ``slice``, against the box's own slice cut to the scene (BuildingProcess.py:140-145)."""
+    sl = _slice_pair(slice)
+    e = int(expand)
+    if e < 0:
+        raise ValueError('expand %d is negative' % e)
+    region = np.zeros((H, W), dtype=np.uint8)
+    for min_y, min_x, max_y, max_x in np.asarray(boxes, dtype=np.int64).reshape(-1, 4).tolist():
+        y0, x0, y1, x1 = 0, 0, H, W
+        if sl:
+            y0, x0 = min_y // sl[0] * sl[0], min_x // sl[1] * sl[1]
+            y1, x1 = min(y0 + sl[0], H), min(x0 + sl[1], W)
+        min_y = min_y - e if (min_y - e) > y0 else y0
+        min_x = min_x - e if (min_x - e) > x0 else x0
+        max_y = max_y + e if (max_y + e) < y1 else y1
+        max_x = max_x + e if (max_x + e) < x1 else x1
+        region[min_y:max_y, min_x:max_x] = 255
+    return region
+
+
+def region_map_host(ref, expand=10, thresh=0, slice=None, connectivity=2):
+    """The region supervision map of a change map in plain NumPy / Python: uint8 (1,H,W), 255 inside the grown bounding box of
+    every connected component of ``double(ref) > thresh`` (NaN: background), 0 elsewhere.  Never touches the device: the oracle
+    of :func:`region_map`."""
+    a = _plane(read_tiff(ref) if isinstance(ref, str) else ref)
+    with np.errstate(invalid='ignore'):
+        fg = a.astype(np.float64) > float(thresh)
+    labels, K = label_components_host(fg, connectivity, slice)
+    return region_paint_host(component_boxes_host(labels, K), a.shape[0], a.shape[1], expand, slice)[None]
+
+
+def _region_on_device(plane, sample_type, thresh, expand, slice, connectivity=2):
+    """(H,W) device plane -> uint8 (1,H,W) region map on the device: label, boxes, paint (``_ops``)."""
+    from . import _ops as ops
+    labels, K = ops.label_components(plane, thresh, sample_type=sample_type, connectivity=connectivity, slice=slice)
+    boxes = ops.component_boxes(labels, K)
+    return ops.region_paint(boxes, labels.shape[0], labels.shape[1], expand, slice=slice)[None]
+
+
+def region_map(ref, expand=10, thresh=0, slice=None, device='cuda', sample_type=None):
+    """:func:`region_map_host` on the device (``_ops.label_components`` / ``component_boxes`` / ``region_paint``): ``ref`` is a
+    (1,H,W) or (H,W) array, the path of a TIFF, or a device tensor (``sample_type=_ops.SAMPLE_U16`` for uint16 bits held in an
+    int16 tensor); uint8, uint16 or float32 samples.  Returns the uint8 (1,H,W) 0 / 255 map as a NumPy array for host input and
+    as a device tensor for device input."""
+    from . import _ops as ops
+    if torch.is_tensor(ref) and ref.is_cuda:
+        t = ref[0] if ref.dim() == 3 and ref.shape[0] == 1 else ref
+        return _region_on_device(t, sample_type, thresh, expand, slice)
+    a = _plane(read_tiff(ref) if isinstance(ref, str) else (ref.numpy() if torch.is_tensor(ref) else ref))
+    if a.dtype == np.bool_:
+        a = a.view(np.uint8)
+    if a.dtype not in (np.uint8, np.uint16, np.float32):
+        raise ops._lib.FcdError('region_map: the change map must hold uint8, uint16 or float32 samples, got %s' % a.dtype)
+    device = ops._upload_device(device, 'the change map goes')
+    st = {1: ops.SAMPLE_U8, 2: ops.SAMPLE_U16, 4: ops.SAMPLE_F32}[a.dtype.itemsize]
+    a = np.ascontiguousarray(a)
+    t = torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(device)
+    return _region_on_device(t, st, thresh, expand, slice).cpu().numpy()
+
+
+def slice_change_labels(boxes_or_ref, slice, shape, thresh=0):
+    """The (ny,nx) 0 / 1 array of BuildingProcess.py:129 for a scene of ``shape`` = (H,W) cut into ``slice`` = (slice_h, slice_w):
+    a slice is 1 when it holds any foreground.  From the (K,4) component boxes labelled WITH that slice (every box then lies in
+    one slice) this is a few lines on the host; a change map of ``shape`` (or (1,H,W)) is thresholded here (``> thresh``)."""
+    sh, sw = _slice_pair(slice)
+    H, W = (int(v) for v in shape)
+    a = boxes_or_ref.cpu().numpy() if torch.is_tensor(boxes_or_ref) else np.asarray(boxes_or_ref)
+    out = np.zeros((-(-H // sh), -(-W // sw)), dtype=np.int64)
+    if a.shape in ((H, W), (1, H, W)):
+        with np.errstate(invalid='ignore'):
+            y, x = np.nonzero(_plane(a).astype(np.float64) > float(thresh))
+    elif a.ndim == 2 and a.shape[1] == 4:
+        y, x = a[:, 0], a[:, 1]
+    else:
+        raise ValueError('slice_change_labels: (K,4) boxes or a change map of shape %s, got shape %s' % ((H, W), a.shape))
+    out[np.asarray(y) // sh, np.asarray(x) // sw] = 1
+    return out
+
+
+def write_label_txt(path, labels, slice, ext='.tif'):
+    """label.txt as BuildingProcess.py:167 writes it: one line ``'{x}_{y}{ext},0,0,{label}'`` per slice, named by the slice's
+    first pixel, x outer and y inner (BuildingProcess.py:99-100).  ``labels`` = the (ny,nx) array of :func:`slice_change_labels`."""
+    sh, sw = _slice_pair(slice)
+    labels = np.asarray(labels)
+    with open(path, 'w') as f:
+        for i in range(labels.shape[1]):
+            for j in range(labels.shape[0]):
+                f.write('{}_{}{},0,0,{}\n'.format(i * sw, j * sh, ext, int(labels[j, i])))
+
+
 # ------------------------------------------------------------------------ dataset
 def _load_scenes(scene_x, scene_y, ref=None, region=None, as_arrays=False):
     """The scene pair and its optional (1,H,W) maps, each given as a (bands,H,W) array or as the path of a TIFF: read, and
@@ -331,14 +515,18 @@ class ResidentScene:
     staging).  The reference map goes up as float32, the form the stitch kernel compares in; the optional weak ``region`` mask
     (GDALDataset_RSS, data_utils.py:239-290) stays in its own sample type.  One scene; several of them make a
     ``ResidentSceneSet``, the training feed.  ``stats='auto'``: the scene's own statistics (:meth:`statistics`), taken on the
-    device before anything is cut."""
+    device before anything is cut.  ``region='derive'``: the region map is made from the reference map on the device
+    (:meth:`derive_region` with ``region_thresh``, ``region_expand``, ``region_slice``)."""
 
     def __init__(self, scene_x, scene_y, ref=None, patch_size=(200, 200), overlap_padding=(10, 10), stats=None, device='cuda',
-                 region=None, enhance=None):
+                 region=None, enhance=None, region_thresh=0, region_expand=10, region_slice=None):
         from . import _ops as ops
         if stats is not None and enhance is not None:
             raise ValueError('ResidentScene: give stats (NORMALIZE) or enhance, not both')
-        scene_x, scene_y, ref, region = _load_scenes(scene_x, scene_y, ref, region, as_arrays=True)
+        derive = isinstance(region, str) and region == 'derive'
+        if derive and ref is None:
+            raise ValueError("ResidentScene: region='derive' needs the reference map")
+        scene_x, scene_y, ref, region = _load_scenes(scene_x, scene_y, ref, None if derive else region, as_arrays=True)
         if scene_x.dtype != scene_y.dtype or scene_x.dtype not in (np.uint8, np.uint16, np.float32):
             raise ops._lib.FcdError('ResidentScene: both scenes must be uint8, uint16 or float32 arrays of one type, got %s / %s'
                                     % (scene_x.dtype, scene_y.dtype))
@@ -358,14 +546,22 @@ class ResidentScene:
                      0 if region is None else sample_type[region.dtype.itemsize], patch_size, overlap_padding, stats)
         if enhance is not None:
             self.set_enhance(enhance)
+        if derive:
+            self.derive_region(region_thresh, region_expand, region_slice)
 
     @classmethod
     def from_device(cls, x, y, ref=None, region=None, patch_size=(200, 200), overlap_padding=(10, 10), stats=None,
-                    sample_type=None, ref_type=None, region_type=None):
+                    sample_type=None, ref_type=None, region_type=None, region_thresh=0, region_expand=10, region_slice=None):
         """A ResidentScene over tensors that already live on the device, copied nowhere: ``x``, ``y`` (C,H,W) of uint8, uint16 or
         float32 samples (``sample_type=_ops.SAMPLE_U16`` for uint16 bits held in an int16 tensor), ``ref`` / ``region`` (1,H,W)
-        likewise (``ref_type`` / ``region_type``).  The stitch kernel of ``infer_scene_resident`` wants a float32 ``ref``."""
+        likewise (``ref_type`` / ``region_type``).  The stitch kernel of ``infer_scene_resident`` wants a float32 ``ref``.
+        ``region='derive'``: as in the constructor."""
         from . import _ops as ops
+        derive = isinstance(region, str) and region == 'derive'
+        if derive:
+            if ref is None:
+                raise ValueError("ResidentScene: region='derive' needs the reference map")
+            region = None
         x, y, st, _, _, _ = ops._scene_pair('ResidentScene', x, y, sample_type, one_device=True)
         maps = []
         for t, typ, name in ((ref, ref_type, 'reference map'), (region, region_type, 'region map')):
@@ -379,6 +575,8 @@ class ResidentScene:
         self = cls.__new__(cls)
         self.device = x.device
         self._attach(x, y, st, maps[0], maps[1], maps[2], maps[3], patch_size, overlap_padding, stats)
+        if derive:
+            self.derive_region(region_thresh, region_expand, region_slice)
         return self
 
     def _attach(self, x, y, sample_type, ref, ref_type, region, region_type, patch_size, overlap_padding, stats):
@@ -422,6 +620,20 @@ class ResidentScene:
         self._stats_dev = torch.from_numpy(np.ascontiguousarray(enh.params(self.bands))).to(self.device)
         self.enhance, self.enhance_kind = enh, int(enh.kind)
         self.enhance_scale = (float(enh.scale[0]), float(enh.scale[1])) if enh.kind == 3 else None
+
+    def derive_region(self, thresh, expand=10, slice=None):
+        """Make the region map from the reference map where it lies (:func:`region_map`: components of ``ref > thresh``, their
+        boxes grown by ``expand``; ``slice`` = (slice_h, slice_w) for the sliced recipe) and install it as ``self.region``, uint8
+        (1,H,W) of 0 / 255.  OSCD: ``thresh=1``; WHU: ``thresh=0, slice=(200, 200)``.  A scene that already belongs to a
+        ``ResidentSceneSet`` needs the set's ``refresh()`` afterwards: the set keeps the address of the map it was made with."""
+        from . import _ops as ops
+        if self.ref is None:
+            raise ValueError('ResidentScene.derive_region needs the reference map')
+        plane = self.ref.reshape(self.grid.ysize, self.grid.xsize)
+        self.region = _region_on_device(plane, self.ref_type, thresh, expand, slice)
+        self.region_type = ops.SAMPLE_U8
+        self._solo = None                # a private one-scene set holds the old map's address
+        return self.region
 
     def maxmin(self, overlap_padding=(0, 0)):
         """Two lists of ``[min, max]`` per band, of scene x and of scene y: the TRUE masked extrema over the tiling of this scene
@@ -562,14 +774,15 @@ class ResidentSceneSet:
         self.device, self.bands, self.sample_type = first.x.device, first.bands, first.sample_type
         self.patch_size, self.pad = first.grid.patch_size, first.grid.pad
         self.table = ops.scene_set_table([s.grid for s in self.scenes])
-        self.has_ref = any(s.ref is not None for s in self.scenes)
-        self.has_region = any(s.region is not None for s in self.scenes)
         self.refresh()
 
     def refresh(self):
-        """Rebuild the descriptor table and the statistics array from the scenes' current tensors and statistics."""
+        """Rebuild the descriptor table and the statistics array from the scenes' current tensors and statistics (after
+        ``ResidentScene.set_stats`` / ``set_enhance`` / ``derive_region`` on a scene of the set)."""
         C = self.bands
         check_scene_set(self.scenes)
+        self.has_ref = any(s.ref is not None for s in self.scenes)
+        self.has_region = any(s.region is not None for s in self.scenes)
         kinds = [(s.enhance_kind, s.enhance_scale) for s in self.scenes if s.enhance_kind]
         self.mode, self.scale = (kinds[0][0], kinds[0][1] or (-1.0, 1.0)) if kinds else (1, (-1.0, 1.0))
         rows, stats = [], []

@@ -515,6 +515,33 @@ size_t fcd_scene_minmax_ws_bytes(int C, int n, int ph);
 int fcd_scene_minmax(const void* scene_x, const void* scene_y, int sample_type, int C, int H, int W, const int32_t* table,
                      int n, int ph, int pw, float* out, unsigned long long* count, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- region supervision maps from a change map (csrc/regions.hip) ---------------
+ * What the reference prepares offline with skimage (OSCDProcess.py:56-73, BuildingProcess.py:127-145): threshold the change
+ * map, label its connected components, take their bounding boxes, grow every box by `expand` pixels, clamp it and fill it
+ * with 255.  The caller owns every buffer; labels + workspace take at most 8 bytes per pixel.  H*W <= 2^31 - 1.
+ *
+ * fcd_label_components: map = one plane of H*W samples of sample_type (FCD_SAMPLE_*; uint16 may arrive as int16 bits).
+ *   Foreground is (double)v > thresh; a NaN is background.  connectivity: 2 = 8 neighbours (measure.label(connectivity=2),
+ *   the reference's), 1 = 4 neighbours.  slice_h, slice_w > 0 cut connectivity at slice borders -- (y,x) and (y',x') are
+ *   joined only if y / slice_h == y' / slice_h and x / slice_w == x' / slice_w, BuildingProcess's per-slice labelling on the
+ *   unsliced scene; 0, 0 = one slice.  labels: H*W int32, every element written: 0 = background, 1..K otherwise, the
+ *   components numbered in raster order of their first pixel (scipy.ndimage.label's numbering).  count: one int32 on the
+ *   device = K.  ws: fcd_label_components_ws_bytes(H, W) bytes (0 for a size that is refused).  Union-find whose parents only
+ *   ever fall (integer atomicMin), phases at kernel boundaries, no host read-back: the result is the same bit for bit from
+ *   run to run. */
+size_t fcd_label_components_ws_bytes(int H, int W);
+int fcd_label_components(const void* map, int sample_type, int H, int W, double thresh, int connectivity, int slice_h,
+                         int slice_w, int32_t* labels, int32_t* count, void* ws, size_t ws_bytes, void* stream);
+/* boxes: int32 (K,4) = min_y, min_x, max_y, max_x, half-open like regionprops.bbox (OSCDProcess.py:63-66); row k is label
+ * k + 1.  Every element is written (no memset by the caller); 16-byte aligned.  Integer atomic min / max: order-independent. */
+int fcd_component_boxes(const int32_t* labels, int H, int W, int K, int32_t* boxes, void* stream);
+/* region: H*W uint8, every element written: 255 inside any grown box, 0 elsewhere.  Growth and clamp are the reference's
+ * (OSCDProcess.py:68-71, BuildingProcess.py:140-143), against the rectangle of the box's slice intersected with the scene, or
+ * against the scene without slices:  lo = lo - e if lo - e > lo_bound else lo_bound;  hi = hi + e if hi + e < hi_bound else
+ * hi_bound.  expand >= 0.  Overlapping boxes store the same byte. */
+int fcd_region_paint(const int32_t* boxes, int K, int H, int W, int expand, int slice_h, int slice_w, uint8_t* region,
+                     void* stream);
+
 /* ---- loss terms ------------------------------------------------------------
  * Masked per-sample sums -- the reconstruction terms of Loss.py:76-84 (L1) and
  * :110-119 (MSE), and region_loss Loss.py:127-141:
