@@ -168,6 +168,8 @@ _SIGS = {
     'fcd_tile_confusion': (c_int, [P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, P, P]),
     'fcd_tile_confusion_items': (c_int, [P, P, P, c_int, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, P, P]),
     'fcd_scene_set_cut': (c_int, [P, c_int, c_int, c_int, P, c_int, P, c_int, c_int, c_int, P, P, P, P, P, P, P]),
+    'fcd_scene_set_stitch': (c_int, [P, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float,
+                                     c_float, c_int, P, c_int64, P, P, P, P]),
     'fcd_scene_stats_ws_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
     'fcd_scene_stats': (c_int, [P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, P, P, c_size_t, P]),
     'fcd_scene_set_cut_aug': (c_int, [P, c_int, c_int, c_int, P, c_int, P, c_int, c_int, c_int, P, c_int, c_double, c_double, P, c_int,

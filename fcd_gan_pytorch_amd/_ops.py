@@ -1791,6 +1791,10 @@ class SceneSetTable:
         self.rects = np.ascontiguousarray(rc.astype(np.int32))
         self._dev = {}
 
+        # where scene s lies in the flat maps of the set stitch; scene_set_table replaces this with the offsets of its grids
+        self.offsets = scene_map_offsets(self.sizes)
+        self._dev_off = {}
+
     def __len__(self):
         return self.rows.shape[0]
 
@@ -1800,6 +1804,52 @@ class SceneSetTable:
         if device not in self._dev:
             self._dev[device] = (torch.from_numpy(self.rows).to(device), torch.from_numpy(self.rects).to(device))
         return self._dev[device]
+
+    def map_offsets(self, device):
+        """The map offsets (int64[S+1]) on ``device``: validated against the scene sizes, then uploaded once."""
+        device = _upload_device(device, 'the map offsets go')
+        if device not in self._dev_off:
+            validate_map_offsets(self.offsets, self.sizes)
+            self._dev_off[device] = torch.from_numpy(self.offsets).to(device)
+        return self._dev_off[device]
+
+
+def _grid_size(g):
+    """(W, H) of a ``tiles.TileGrid`` or of a (W, H) pair."""
+    return (int(g.xsize), int(g.ysize)) if hasattr(g, 'xsize') else (int(g[0]), int(g[1]))
+
+
+def scene_map_offsets(grids):
+    """Host int64[S+1]: where the (H,W) map of every scene starts in ONE flat buffer that holds them end to end, and the total
+    behind the last -- prefix sums of H*W over ``grids`` (``tiles.TileGrid`` each, or (W, H) pairs).  Pure host code."""
+    import numpy as np
+    off = np.zeros(len(grids) + 1, dtype=np.int64)
+    for s, g in enumerate(grids):
+        w, h = _grid_size(g)
+        off[s + 1] = off[s] + w * h
+    return off
+
+
+def validate_map_offsets(offsets, sizes):
+    """Raise FcdError unless ``offsets`` is an integer array of S + 1 entries that starts at 0, never decreases and spans
+    exactly H*W for every scene of ``sizes`` = [(W, H)]: what keeps fcd_scene_set_stitch inside its two buffers.  Pure host code."""
+    import numpy as np
+    off = np.asarray(offsets)
+    sizes = [_grid_size(g) for g in sizes]
+    if off.ndim != 1 or off.dtype.kind not in 'iu' or off.shape[0] != len(sizes) + 1 or not sizes:
+        raise _lib.FcdError('map offsets: expected %d integer entries for %d scenes, got %s of shape %s'
+                            % (len(sizes) + 1, len(sizes), off.dtype, off.shape))
+    off = off.astype(np.int64)
+    if off[0] != 0:
+        raise _lib.FcdError('map offsets: the first scene must start at 0, not %d' % off[0])
+    span = np.diff(off)
+    if (span < 0).any():
+        raise _lib.FcdError('map offsets: decreasing at scene %d (%s)' % (int(np.argmax(span < 0)), off.tolist()))
+    want = np.array([w * h for w, h in sizes], dtype=np.int64)
+    if (span != want).any():
+        s = int(np.argmax(span != want))
+        raise _lib.FcdError('map offsets: scene %d spans %d elements, its map has %d x %d = %d'
+                            % (s, span[s], sizes[s][1], sizes[s][0], want[s]))
 
 
 def scene_set_table(grids):
@@ -1814,24 +1864,29 @@ def scene_set_table(grids):
             rows.append(sum((list(t) for t in g.slices(i)), []) + [s])
             rects.append(g.eff_range(i))
     (patch, pad), = geoms
-    return SceneSetTable(np.array(rows, dtype=np.int64).reshape(-1, 13), rects, [(g.xsize, g.ysize) for g in grids], patch, pad)
+    table = SceneSetTable(np.array(rows, dtype=np.int64).reshape(-1, 13), rects, [(g.xsize, g.ysize) for g in grids], patch, pad)
+    table.offsets = scene_map_offsets(grids)     # from the grids the rows came from; checked against the sizes before upload
+    validate_map_offsets(table.offsets, table.sizes)
+    return table
 
 
 class TileIndex:
     """A list of rows of a resident table, validated on the host (every entry in [0, size)) and uploaded ONCE, from pinned
-    memory without making the host wait; ``index[a:b]`` is a view of the device copy -- a batch of an epoch's plan."""
+    memory without making the host wait; ``index[a:b]`` is a view of the device copy -- a batch of an epoch's plan.  ``host``
+    keeps the validated entries (int32, a view for a slice): what the set stitch checks for repeats without asking the device."""
 
     def __init__(self, items, size, device=None, _view=None):
         import numpy as np
         if _view is not None:
-            self.size, self.dev = size, _view
+            self.size, self.dev, self.host = size, _view, None           # a slice: __getitem__ hands the host view over
             return
         a = np.asarray(items, dtype=np.int64).reshape(-1)
         if a.size == 0 or (a < 0).any() or (a >= size).any():
             raise _lib.FcdError('tile index: %d entries, all must lie in [0, %d)' % (a.size, size))
         device = _upload_device(device, 'the tile index goes')
         self.size = int(size)
-        self.dev = torch.from_numpy(a.astype(np.int32)).pin_memory().to(device, non_blocking=True)
+        self.host = a.astype(np.int32)
+        self.dev = torch.from_numpy(self.host).pin_memory().to(device, non_blocking=True)
 
     def __len__(self):
         return self.dev.shape[0]
@@ -1839,7 +1894,9 @@ class TileIndex:
     def __getitem__(self, s):
         if not isinstance(s, slice) or s.step not in (None, 1):
             raise TypeError('TileIndex takes contiguous slices')
-        return TileIndex(None, self.size, _view=self.dev[s])
+        part = TileIndex(None, self.size, _view=self.dev[s])
+        part.host = None if self.host is None else self.host[s]
+        return part
 
     def on(self, device):
         if self.dev.device != torch.device(device) and torch.device(device).index is not None:
@@ -1983,6 +2040,81 @@ def scene_set_cut(descs, table, index, C, sample_type, stats=None, want_ref=True
     check(getattr(lib, fn)(_p(descs), S, sample_type, C, _p(tab), len(table), _p(index.on(dev)), n, ph, pw, _p(s), *aug,
                            *(_p(t) for t in out), _stream()), fn)
     return out
+
+
+class SceneSetMaps:
+    """The output maps of a scene set: ``flat_density`` / ``flat_color`` = ONE zeroed float32 device buffer each that holds the
+    maps of all scenes end to end, ``offsets`` = the resident int64[S+1] of where each starts (``SceneSetTable.map_offsets``),
+    ``density[s]`` / ``color[s]`` = (1,H_s,W_s) views of the buffers.  Made by ``tiles.ResidentSceneSet.new_maps``."""
+
+    def __init__(self, table, device):
+        if not isinstance(table, SceneSetTable):
+            raise _lib.FcdError('SceneSetMaps: pass the SceneSetTable of the set')
+        self.table, self.offsets = table, table.map_offsets(device)
+        off = table.offsets
+        self.total = int(off[-1])
+        self.flat_density = torch.zeros(self.total, dtype=torch.float32, device=self.offsets.device)
+        self.flat_color = torch.zeros(self.total, dtype=torch.float32, device=self.offsets.device)
+        self.density = [self.flat_density[int(off[s]):int(off[s + 1])].view(1, h, w) for s, (w, h) in enumerate(table.sizes)]
+        self.color = [self.flat_color[int(off[s]):int(off[s + 1])].view(1, h, w) for s, (w, h) in enumerate(table.sizes)]
+
+    @property
+    def device(self):
+        return self.flat_density.device
+
+
+def check_unique_items(items, n):
+    """Raise FcdError when an item appears twice among the first ``n`` of the host index list ``items``: two tiles that own the
+    same pixels in one launch would make the stitched maps depend on the order the workgroups arrive in.  Pure host code."""
+    import numpy as np
+    a = np.asarray(items).reshape(-1)
+    n = int(n)
+    if not 0 < n <= a.size:
+        raise _lib.FcdError('scene_set_stitch: n = %d with %d indices' % (n, a.size))
+    vals, cnt = np.unique(a[:n], return_counts=True)
+    if (cnt > 1).any():
+        raise _lib.FcdError('scene_set_stitch: item %d appears %d times among the first %d tiles; every item may be stitched '
+                            'once per launch' % (int(vals[np.argmax(cnt > 1)]), int(cnt.max()), n))
+
+
+@torch.no_grad()
+def scene_set_stitch(cmap, descs, table, index, maps, n=None, prob_thresh=0.5, gt_map=(1, 2), pre_map=(0, 1), write_color=True,
+                     scene_counts=None):
+    """Write the owned centres of the first ``n`` tiles of ``cmap`` (N,1,ph,pw) -- tile t = row ``index[t]`` (a
+    :class:`TileIndex`) of ``table`` (a :class:`SceneSetTable`) -- into ``maps`` (a :class:`SceneSetMaps` of this table, updated
+    in place): every tile into the maps of ITS scene, colour-coded against that scene's resident reference map (any sample
+    type; a scene without one gets 1 where a change was detected) and counted into its row of ``scene_counts`` (device int64
+    (S,4), accumulated in place; cell order of Evaluator.add_batch_map; the rows sum to the overall matrix).  One launch
+    (fcd_scene_set_stitch).  ``n <= len(index)``: the trailing padded duplicates are not stitched; an item may appear only once
+    among the first ``n``."""
+    if not isinstance(table, SceneSetTable) or not isinstance(index, TileIndex) or index.size != len(table) or index.host is None:
+        raise _lib.FcdError('scene_set_stitch: pass a SceneSetTable and a TileIndex validated against it')
+    S = len(table.sizes)
+    if not torch.is_tensor(descs) or not descs.is_cuda or descs.dtype != torch.int64 or \
+            tuple(descs.shape) != (S, SCENE_DESC_COLS) or not descs.is_contiguous():
+        raise _lib.FcdError('scene_set_stitch: descs must be a contiguous device int64 (%d, %d) tensor' % (S, SCENE_DESC_COLS))
+    dev = descs.device
+    cmap = _dev(cmap, 'cmap')
+    (pw, ph), (padx, pady) = table.patch, table.pad
+    if cmap.dim() != 4 or cmap.shape[1] != 1 or tuple(cmap.shape[2:]) != (ph, pw) or cmap.device != dev:
+        raise _lib.FcdError('scene_set_stitch: cmap must be (N,1,%d,%d) on %s, got %s on %s'
+                            % (ph, pw, dev, tuple(cmap.shape), cmap.device))
+    n = len(index) if n is None else int(n)
+    if not 0 < n <= min(len(index), cmap.shape[0]):
+        raise _lib.FcdError('scene_set_stitch: n = %d with %d indices and %d tiles' % (n, len(index), cmap.shape[0]))
+    check_unique_items(index.host, n)
+    if not isinstance(maps, SceneSetMaps) or maps.table is not table or maps.device != dev:
+        raise _lib.FcdError('scene_set_stitch: maps must be the SceneSetMaps of this set on %s (ResidentSceneSet.new_maps)' % dev)
+    if scene_counts is not None:
+        if not torch.is_tensor(scene_counts) or not scene_counts.is_cuda or scene_counts.dtype != torch.int64 or \
+                tuple(scene_counts.shape) != (S, 4) or not scene_counts.is_contiguous() or scene_counts.device != dev:
+            raise _lib.FcdError('scene_set_stitch: scene_counts must be a contiguous int64 (%d, 4) tensor on %s' % (S, dev))
+    tab, _ = table.to(dev)
+    check(lib.fcd_scene_set_stitch(_p(cmap), _p(descs), S, _p(tab), len(table), _p(index.on(dev)), n, ph, pw, padx, pady,
+                                   float(prob_thresh), float(gt_map[0]), float(gt_map[1]), float(pre_map[0]), float(pre_map[1]),
+                                   1 if write_color else 0, _p(maps.offsets), maps.total, _p(maps.flat_density),
+                                   _p(maps.flat_color), _p(scene_counts), _stream()), 'fcd_scene_set_stitch')
+    return maps
 
 
 # ------------------------------------------------------- region maps from a change map (csrc/regions.hip)

@@ -457,6 +457,98 @@ extern "C" int fcd_scene_set_cut_aug(const fcd_scene_desc* descs, int S, int sam
                        SceneAugArgs{mode, R, s0, s1, erase}, x, y, ref_tiles, region_tiles, valid, stream);
 }
 
+// ---- set stitch ------------------------------------------------------------------------------------------------------
+// fcd_scene_stitch for a batch whose tiles come from S resident scenes: the inference side of the set.  The maps of all scenes
+// lie end to end in ONE density and ONE colour buffer, scene s at [map_off[s], map_off[s + 1]); the counters are one row of four
+// per scene.  One wave per (tile, canvas row); the decode index -> row -> scene -> map offset is wave-uniform, and more than
+// that: t depends on blockIdx.y alone, so all 16 waves of a workgroup walk the same tiles and "the scene of this tile differs
+// from the last one's" is WORKGROUP-uniform.  The running totals are flushed through flush_counts at every such change (and at
+// the end) into the row of the scene they belong to; every wave reaches those barriers the same number of times because the row
+// test j >= h comes AFTER the flush.  A tile whose index, scene, map span or owned rectangle does not fit (none passes the
+// host's validation) is skipped as a whole: no store, no count -- and, being a function of t too, no divergent barrier.
+__global__ __launch_bounds__(kCountBlock) void fcd_scene_set_stitch_kernel(
+    const float* __restrict__ cmap, const fcd_scene_desc* __restrict__ descs, int S, const int32_t* __restrict__ table, int T,
+    const int32_t* __restrict__ index, int n, int ph, int pw, int padx, int pady, SceneCountArgs a, int write_color,
+    const long long* __restrict__ map_off, long long total, float* __restrict__ density, float* __restrict__ color,
+    unsigned long long* __restrict__ scene_counts) {
+  const int lane = threadIdx.x & (FCD_WAVE - 1);
+  const int j = wave_row<kCountWaves>();
+  unsigned long long cnt[4] = {0, 0, 0, 0};
+  int cur = -1;                                              // the scene cnt belongs to; workgroup-uniform
+  for (long long t = blockIdx.y; t < n; t += gridDim.y) {
+    const int g = index[t];
+    const bool row_ok = g >= 0 && g < T;
+    const int32_t* __restrict__ row = table + (long long)(row_ok ? g : 0) * TS_COLS;
+    const int s = row[TS_SCENE];
+    bool ok = row_ok && s >= 0 && s < S;
+    const fcd_scene_desc* __restrict__ d = descs + (ok ? s : 0);
+    const long long H = d->H, W = d->W;
+    const long long off = map_off[ok ? s : 0], end = map_off[(ok ? s : 0) + 1];
+    const int x0 = row[T_X0], y0 = row[T_Y0], w = row[T_W], h = row[T_H];
+    ok = ok && off >= 0 && end <= total && H > 0 && W > 0 && end - off == H * W;
+    ok = ok && x0 >= 0 && y0 >= 0 && w >= 0 && h >= 0 && (long long)x0 + w <= W && (long long)y0 + h <= H && padx + w <= pw &&
+         pady + h <= ph;
+    if (!ok) continue;                                       // workgroup-uniform: a function of t alone
+    const bool has_ref = d->ref != 0;
+    const bool counting = has_ref && scene_counts != nullptr;
+    if (counting && s != cur) {                              // workgroup-uniform, in front of the row test: all waves flush
+      if (cur >= 0) {
+        flush_counts(cnt, scene_counts + (long long)cur * 4);
+        __syncthreads();                                     // the LDS partials are free for the next flush
+        cnt[0] = cnt[1] = cnt[2] = cnt[3] = 0;
+      }
+      cur = s;
+    }
+    if (j >= h) continue;                                    // wave-uniform; no barrier between here and the next tile
+    const float* __restrict__ src = cmap + ((t * ph) + pady + j) * pw + padx;
+    const long long rbase = (long long)(y0 + j) * W + x0;    // inside the scene's reference map
+    const long long obase = off + rbase;                     // inside the flat maps
+    const void* __restrict__ ref = (const void*)d->ref;
+    const int rtype = d->ref_type;
+    for (int i0 = 0; i0 < w; i0 += FCD_WAVE) {               // wave-uniform trip count: every lane reaches the ballots
+      const int i = i0 + lane;
+      const bool live = i < w;
+      float p = 0.f, gt = 0.f;
+      if (live) {
+        p = src[i];
+        if (has_ref) gt = load_sample(ref, rbase + i, rtype);
+      }
+      const float pre = threshold(p, a.thresh);
+      float code = 0.f;
+      if (write_color && has_ref) {                          // write_changemap_gdal's assignment order: the later rule wins
+        if (pre == a.pre0 && gt == a.gt1) code = 1.f;        // miss
+        if (pre == a.pre1 && gt == a.gt0) code = 2.f;        // false detection
+        if (pre == a.pre1 && gt == a.gt1) code = 3.f;        // true detection
+      } else if (pre == a.pre1) {
+        code = 1.f;
+      }
+      if (live) {
+        density[obase + i] = p;
+        color[obase + i] = code;
+      }
+      if (counting) count_cells(live, gt, pre, a, cnt);
+    }
+  }
+  if (scene_counts && cur >= 0) flush_counts(cnt, scene_counts + (long long)cur * 4);     // workgroup-uniform
+}
+
+extern "C" int fcd_scene_set_stitch(const float* cmap, const fcd_scene_desc* descs, int S, const int32_t* table, int T,
+                                    const int32_t* index, int n, int ph, int pw, int padx, int pady, float thresh, float gt0,
+                                    float gt1, float pre0, float pre1, int write_color, const int64_t* map_off, int64_t total,
+                                    float* density, float* color, unsigned long long* scene_counts, void* stream) {
+  FCD_CHECK_ARG(cmap && descs && table && index && map_off && density && color && S > 0 && T > 0 && n > 0 && ph > 0 && pw > 0 &&
+                    total > 0 && padx >= 0 && pady >= 0 && 2 * padx < pw && 2 * pady < ph,
+                "fcd_scene_set_stitch: bad arguments");
+  const long long rows = (long long)n * ph;
+  FcdProfScope prof(FCD_K_MISC, (hipStream_t)stream, 0.0, (double)rows * pw * 16.0);
+  const SceneCountArgs a{thresh, gt0, gt1, pre0, pre1};
+  hipLaunchKernelGGL(fcd_scene_set_stitch_kernel, count_grid(ph, n), dim3(kCountBlock), 0, (hipStream_t)stream, cmap, descs, S,
+                     table, T, index, n, ph, pw, padx, pady, a, write_color, (const long long*)map_off, (long long)total, density,
+                     color, scene_counts);
+  FCD_LAUNCH_CHECK("fcd_scene_set_stitch");
+  return FCD_OK;
+}
+
 // ---- the masked scan of the statistics and the extrema -------------------------------------------------------------------
 // Both go over the read rectangles of a tile table under one mask: a pixel counts when the fp32 band sum of scene x is non-zero
 // (NaN != 0: counts), for both scenes, once per tile that reads it.  One wave per (tile, row of the read rectangle): the mask of

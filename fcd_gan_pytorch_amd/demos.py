@@ -12,7 +12,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader
 
-from . import Loss, Module, dp, metrics, optim, steps, tiles
+from . import Loss, Module, datasets, dp, metrics, optim, steps, tiles
 from . import transforms as _transforms
 
 
@@ -296,6 +296,162 @@ def infer_scene_resident(netS, scene, device, batch_size=10, prob_thresh=0.5, gt
     return dict(density=density.cpu().numpy(), color=color.cpu().numpy(), evaluator=acc)
 
 
+def _set_result(names, density, color, scene_counts, has_ref, acc=None):
+    """The dict both set routes return.  ``scene_counts``: (S,4) int64 device counter (row s = scene s) or None; the
+    per-scene evaluators take its rows without a copy, the overall one their sum; a scene without a reference has no counts."""
+    scene_acc = None
+    if scene_counts is not None:
+        scene_acc = [metrics.Evaluator(2) for _ in names]
+        for s, ev in enumerate(scene_acc):
+            if has_ref[s]:
+                ev.attach_counts(scene_counts[s])
+        acc = metrics.Evaluator(2)
+        if any(has_ref):
+            acc.attach_counts(scene_counts.sum(0))
+    return dict(density=density, color=color, evaluator=acc, scene_evaluators=scene_acc, names=list(names))
+
+
+def _no_ref_scores_nothing(has_ref, gt_map):
+    # a scene without a reference gives zero reference tiles: they must not land in a cell
+    if not all(has_ref) and any(float(g) == 0.0 for g in gt_map):
+        raise ValueError('score_only: a scene without a reference map in a set scored against gt_map %r (0 is a class)' % (gt_map,))
+
+
+@torch.no_grad()
+def infer_scene_set(netS, ds, device, batch_size=10, prob_thresh=0.5, gt_map=(1, 2), pre_map=(0, 1), eval_mode=True,
+                    score_only=False):
+    """``infer_scene`` over a ``datasets.MultiSceneDataset``: the reference's test pass and final maps over SEVERAL scenes
+    (Demo_RSSS.py:399-447,451-502).  The tiles are walked in global item order without shuffling, so a batch may hold tiles of
+    two scenes -- with ``eval_mode=False`` (the per-epoch test pass: BatchNorm in train mode) the batch composition is part of
+    the result, which is why this is not a loop of ``infer_scene`` calls.  Returns ``dict(density=[(1,H,W) per scene],
+    color=[...], evaluator=<overall>, scene_evaluators=[per scene], names=...)``; a scene without a reference map gets the
+    detection-only colour code and counts nothing.  ``score_only=True``: counts only (``add_batch_map`` over the owned
+    centres): no maps (``density`` / ``color`` None) and no per-scene evaluators.  Data parallel: as ``infer_scene``."""
+    if not isinstance(ds, datasets.MultiSceneDataset):
+        raise TypeError('infer_scene_set takes a datasets.MultiSceneDataset, got %s' % type(ds).__name__)
+    dev = torch.device(device)
+    if eval_mode:
+        dp.sync_buffers((netS,))
+    was_training = netS.training
+    netS.train(not eval_mode)
+    S = len(ds.scenes)
+    has_ref = [s.ref is not None for s in ds.scenes]
+    if score_only:
+        _no_ref_scores_nothing(has_ref, gt_map)
+    density, color = (None, None) if score_only else (ds.new_outputs(), ds.new_outputs())
+    acc = metrics.Evaluator(2)
+    acc.device_counts(dev)                                  # allocated on every rank: the collectives stay in step
+    scene_counts = None if score_only else torch.zeros((S, 4), dtype=torch.int64, device=dev)
+    for batch, real, _ in _Epoch(ds, batch_size, 0, dev, shuffle=False):
+        x, y, item, r = batch[:4]
+        cmap, mask = steps.infer_density(netS, x, y, prob_thresh)
+        maskf = mask.to(cmap.dtype)
+        items = item.tolist()[:real]                        # padded duplicates belong to another rank
+        scene_of = [ds.locate(it)[0] for it in items]
+        valid = torch.zeros_like(mask, dtype=torch.bool)
+        for i, it in enumerate(items):
+            if has_ref[scene_of[i]]:
+                r0, r1, c0, c1 = ds.eff_range(it)
+                valid[i, :, r0:r1, c0:c1] = True
+        if score_only:
+            acc.add_batch_map(r, maskf, gt_map, pre_map, valid=valid)
+            continue
+        for s in sorted(set(scene_of)):
+            if has_ref[s]:
+                ev = metrics.Evaluator(2)
+                mine = _rows_mask(valid, [i for i, k in enumerate(scene_of) if k == s])
+                ev.add_batch_map(r, maskf, gt_map, pre_map, valid=valid & mine)
+                scene_counts[s] += ev._dev_counts
+        codes = metrics.changemap_codes(maskf, r, True, ref_map=gt_map, dt_map=pre_map)
+        plain = metrics.changemap_codes(maskf, maskf, False, dt_map=pre_map)
+        with_ref = _rows_mask(valid, [i for i, k in enumerate(scene_of) if has_ref[k]])
+        codes = torch.where(with_ref, codes, plain)
+        cm_h, co_h = cmap.cpu().numpy(), codes.cpu().numpy()
+        for i, it in enumerate(items):
+            ds.write_center(density, cm_h[i], it)
+            ds.write_center(color, co_h[i], it)
+    if not score_only and dp.exchanging():
+        sizes = [d.size for d in density]
+        both = torch.from_numpy(np.concatenate([d.ravel() for d in density + color])).to(dev)
+        dp.sum_counts(both)
+        flat = np.split(both.cpu().numpy(), np.cumsum(sizes + sizes)[:-1])
+        density = [f.reshape(d.shape).copy() for f, d in zip(flat[:S], density)]
+        color = [f.reshape(d.shape).copy() for f, d in zip(flat[S:], density)]
+    netS.train(was_training)
+    return _set_result(ds.names, density, color, scene_counts, has_ref, acc)
+
+
+def _rows_mask(like, rows):
+    """(N,1,1,1) bool on ``like``'s device: True for the tiles ``rows`` of the batch."""
+    m = torch.zeros((like.shape[0], 1, 1, 1), dtype=torch.bool, device=like.device)
+    if rows:
+        m[rows] = True
+    return m
+
+
+@torch.no_grad()
+def infer_scene_set_resident(netS, scene_set, device, batch_size=10, prob_thresh=0.5, gt_map=(1, 2), pre_map=(0, 1),
+                             eval_mode=True, score_only=False):
+    """``infer_scene_set`` with the data path on the device: ``scene_set`` is a ``tiles.ResidentSceneSet``.  Same batches
+    (``dp.RankStridedBatches(shuffle=False)`` over the global items, so tiles of different scenes share a batch), the index
+    list uploaded ONCE; per batch one ``fcd_scene_set_cut`` and one ``fcd_scene_set_stitch`` around the Segmentor, which writes
+    every tile into its own scene's maps and counts it into its own scene's row; at the end ONE device-to-host copy per flat
+    map.  Same returned dict, bit for bit.  ``score_only=True``: no maps; the counts come from ``Evaluator.add_tiles`` on the
+    resident rectangles of the set.  Data parallel: each rank stitches its tiles into zeroed maps, the two flat buffers are
+    summed with one ``dp.sum_counts`` and the counters are all-reduced when the scores are read.  There is no ``raw=True``
+    route: the statistics differ per tile of a batch, so NORMALIZE cannot be folded into the first convolution."""
+    if not isinstance(scene_set, tiles.ResidentSceneSet):
+        raise TypeError('infer_scene_set_resident takes a tiles.ResidentSceneSet, got %s' % type(scene_set).__name__)
+    dev = scene_set.device
+    if eval_mode:
+        dp.sync_buffers((netS,))
+    was_training = netS.training
+    netS.train(not eval_mode)
+    S = len(scene_set.scenes)
+    has_ref = [s.ref is not None for s in scene_set.scenes]
+    if score_only:
+        _no_ref_scores_nothing(has_ref, gt_map)
+    acc = metrics.Evaluator(2)
+    acc.device_counts(dev)
+    maps = None if score_only else scene_set.new_maps()
+    scene_counts = None if score_only else torch.zeros((S, 4), dtype=torch.int64, device=dev)
+    plan = tiles.EpochPlan(len(scene_set), batch_size, 0, shuffle=False)
+    index = scene_set.index(plan.flat) if plan.flat else None
+    for b, items in enumerate(plan.batches):
+        part = index[plan.offsets[b]:plan.offsets[b + 1]]
+        real = len(items) - plan.pads[b]                    # padded duplicates belong to another rank
+        x, y, r, _, _ = scene_set.cut(part, want_valid=False)
+        cmap, _ = steps.infer_density(netS, x, y, prob_thresh)
+        if real <= 0:
+            continue
+        if score_only:
+            acc.add_tiles(r, cmap, scene_set.rects(part, real), prob_thresh, gt_map, pre_map)
+        else:
+            scene_set.stitch(cmap, part, maps, n=real, prob_thresh=prob_thresh, gt_map=gt_map, pre_map=pre_map,
+                             write_color=True, scene_counts=scene_counts)
+    density = color = None
+    if not score_only:
+        if dp.exchanging():
+            both = torch.stack([maps.flat_density, maps.flat_color])
+            dp.sum_counts(both)
+        else:
+            both = (maps.flat_density, maps.flat_color)
+        off = scene_set.table.offsets
+        flat_d, flat_c = both[0].cpu().numpy(), both[1].cpu().numpy()       # ONE copy per flat map
+        shapes = [(1, h, w) for w, h in scene_set.table.sizes]
+        density = [flat_d[off[s]:off[s + 1]].reshape(shapes[s]) for s in range(S)]
+        color = [flat_c[off[s]:off[s + 1]].reshape(shapes[s]) for s in range(S)]
+    netS.train(was_training)
+    return _set_result(scene_set.names, density, color, scene_counts, has_ref, acc)
+
+
+def _scores(ev):
+    """The seven scores the reference logs per test pass (Demo_RSSS.py:432-447) as a dict of floats."""
+    miou, ciou = ev.Mean_Intersection_over_Union()
+    return dict(OA=float(ev.Pixel_Accuracy()), Kappa=float(ev.Pixel_Kappa()), precision=float(ev.Pixel_Precision_Rate()),
+                recall=float(ev.Pixel_Recall_Rate()), F1=float(ev.Pixel_F1_score()), mIoU=float(miou), cIoU=float(ciou))
+
+
 def _valid_centres(dataset, like, items, real):
     valid = torch.zeros_like(like, dtype=torch.bool)
     for i, it in enumerate(items[:real]):
@@ -308,7 +464,7 @@ def demo_rsss(dataset, device='cuda', n_channels=4, epochs_g=50, epochs_adv=100,
               learning_rate=5e-5, perception_weight=0.1, ssim_weight=0, perception_perBand=True, l1_weight=0.02,
               g_weight=0.5, d_weight=1, r_weight=2, prob_thresh=0.5, gt_map=(1, 2), pre_map=(0, 1), seed=0,
               netG_state=None, log=None, allow_seeded=False, load_g=None, save_s=None, save_g=None, save_d=None, ragged='pad',
-              region_from_ref=None):
+              region_from_ref=None, test_dataset=None, test_batch_size=None, out_dir=None):
     """Demo_RSSS.py:27-538 on a ``datasets.MultiSceneDataset`` / ``RegionTileDataset`` (tuples
     ``(x, y, item, ref, region)``): G pre-training on the region-masked reconstruction (skipped when a
     generator checkpoint is given -- ``load_g``: path of a ``GModel.pkl`` as the reference writes it,
@@ -319,9 +475,29 @@ def demo_rsss(dataset, device='cuda', n_channels=4, epochs_g=50, epochs_adv=100,
     then cut on the device (``ResidentSceneSet.epoch``) and the accuracy is one ``Evaluator.add_tiles`` call per batch on
     resident rectangles -- no host work per tile, no copy per batch.  ``region_from_ref=(thresh, expand)``: a resident scene that
     has a reference map but no region map gets one derived from it on the device (``ResidentScene.derive_region``: what
-    OSCDProcess.py:56-73 prepares offline; OSCD's recipe is ``(1, 10)``); the default None keeps the error."""
+    OSCDProcess.py:56-73 prepares offline; OSCD's recipe is ``(1, 10)``); the default None keeps the error.
+    ``test_dataset``: a ``tiles.ResidentSceneSet`` or a ``datasets.MultiSceneDataset`` of several scenes, held either way
+    whatever the training set is (``infer_scene_set_resident`` / ``infer_scene_set``; batches of ``test_batch_size``, default
+    ``batch_size``).  After every adversarial epoch it is scored as the reference does (Demo_RSSS.py:399-447): counts only, under
+    ``no_grad`` (same values, no tape) and with ``netS`` in TRAIN mode as there -- so the BatchNorm running statistics of
+    ``netS`` move with the test batches, and the tiles of a batch, which may belong to two scenes, are normalised together.
+    ``history['test']`` gets one dict per epoch: OA, Kappa, precision, recall, F1, mIoU, cIoU.  After the last epoch and the
+    buffer broadcast a full eval-mode pass makes the per-scene density and colour maps (Demo_RSSS.py:451-502): its result is
+    returned under ``test``, and with ``out_dir`` rank 0 writes ``<name>_density.tif`` and ``<name>_binary.tif`` per scene.
+    Without ``test_dataset`` nothing of this happens and the returned dict has no ``test`` key."""
     dev = torch.device(device)
     resident = isinstance(dataset, tiles.ResidentSceneSet)
+    test_pass = None
+    if test_dataset is not None:
+        if isinstance(test_dataset, tiles.ResidentSceneSet):
+            test_route = infer_scene_set_resident
+        elif isinstance(test_dataset, datasets.MultiSceneDataset):
+            test_route = infer_scene_set
+        else:
+            raise TypeError('test_dataset: a tiles.ResidentSceneSet or a datasets.MultiSceneDataset, got %s'
+                            % type(test_dataset).__name__)
+        test_pass = lambda **kw: test_route(netS, test_dataset, dev, batch_size=test_batch_size or batch_size,
+                                            prob_thresh=prob_thresh, gt_map=gt_map, pre_map=pre_map, **kw)
     if resident:
         if region_from_ref is not None:
             todo = [s for s in dataset.scenes if s.region is None and s.ref is not None]
@@ -382,12 +558,24 @@ def demo_rsss(dataset, device='cuda', n_channels=4, epochs_g=50, epochs_adv=100,
         hist['adv'].append([float(v) for v in _epoch_mean(sums)] + [float(acc.Pixel_F1_score())])
         if log:
             log('adv epoch %d d %.4f s %.4f g %.4f F1 %.4f' % ((ep + 1,) + tuple(hist['adv'][-1])))
+        if test_pass is not None:                                                 # Demo_RSSS.py:399-447: netS stays in train mode
+            hist.setdefault('test', []).append(_scores(test_pass(eval_mode=False, score_only=True)['evaluator']))
+            if log:
+                log('adv epoch %d test F1 %.4f' % (ep + 1, hist['test'][-1]['F1']))
     dp.sync_buffers((netS, netG, netD))      # the saved .pkl = the statistics every rank infers with from here on
     _save(netS, save_s)
     _save(netG, save_g)
     _save(netD, save_d)
-    return dict(netS=netS, netD=netD, netG=netG, history=hist, evaluator=acc,
-                vgg_pretrained=crit.loss_perception.pretrained)
+    res = dict(netS=netS, netD=netD, netG=netG, history=hist, evaluator=acc, vgg_pretrained=crit.loss_perception.pretrained)
+    if test_pass is not None:                                                     # Demo_RSSS.py:451-502
+        hist.setdefault('test', [])
+        res['test'] = test = test_pass(eval_mode=True)
+        if out_dir and dp.world_info()[0] == 0:
+            os.makedirs(out_dir, exist_ok=True)
+            for name, den, col in zip(test['names'], test['density'], test['color']):
+                tiles.write_tiff(os.path.join(out_dir, '%s_density.tif' % name), den)
+                tiles.write_tiff(os.path.join(out_dir, '%s_binary.tif' % name), col)
+    return res
 
 
 def demo_wsss(changed_ds, unchanged_ds, device='cuda', n_channels=3, epochs_g=50, epochs_adv=50, unc_batch_size=50,

@@ -73,6 +73,15 @@ class Evaluator:
             self._dev_counts = torch.zeros(4, dtype=torch.int64, device=device)
         return self._dev_counts
 
+    def attach_counts(self, counts):
+        """Take ``counts`` -- a device int64 tensor of 4 elements, e.g. row s of the (S,4) per-scene counter that
+        ``fcd_scene_set_stitch`` accumulates into, or the sum of its rows -- as this evaluator's device counter, without a copy:
+        a view stays a view, so what a kernel adds to the row later is seen here until the scores are read.  Returns self."""
+        if not torch.is_tensor(counts) or counts.dtype != torch.int64 or counts.numel() != 4:
+            raise ValueError('attach_counts: an int64 tensor of 4 elements, got %r' % (counts,))
+        self._dev_counts = counts.reshape(4)
+        return self
+
     def add_tiles(self, ref_tiles, cmap, rects, prob_thresh=0.5, gt_map=(0, 1), pre_map=(0, 1)):
         """``add_batch_map(ref_tiles, cmap > prob_thresh, gt_map, pre_map, valid=<rects>)`` as ONE kernel: the density tiles
         ``cmap`` (N,1,H,W) are thresholded, compared with the reference tiles and counted over ``rects`` = (r0, r1, c0, c1) per

@@ -849,6 +849,22 @@ class ResidentSceneSet:
                                  stats=None if raw else self._stats_dev, want_valid=want_valid, out=out, mode=self.mode,
                                  scale=self.scale, erase=erase)
 
+    def new_maps(self):
+        """The zeroed output maps of the set (``_ops.SceneSetMaps``): one flat density and one flat colour buffer that hold the
+        maps of all scenes end to end, the resident offsets, and ``density[s]`` / ``color[s]`` as (1,H_s,W_s) views."""
+        from . import _ops as ops
+        return ops.SceneSetMaps(self.table, self.device)
+
+    def stitch(self, cmap, index, maps, n=None, prob_thresh=0.5, gt_map=(1, 2), pre_map=(0, 1), write_color=True,
+               scene_counts=None):
+        """Write the owned centres of the first ``n`` density tiles ``cmap`` -- tile t = global item ``index[t]`` (the
+        ``TileIndex`` of :meth:`index`, or a list) -- into ``maps`` (:meth:`new_maps`), each into its own scene's maps,
+        colour-coded against that scene's reference map and counted per scene into ``scene_counts`` (device int64 (S,4)): one
+        launch for tiles of several scenes (``_ops.scene_set_stitch``), the way out of what :meth:`cut` is the way in."""
+        from . import _ops as ops
+        return ops.scene_set_stitch(cmap, self._descs, self.table, self.index(index), maps, n=n, prob_thresh=prob_thresh,
+                                    gt_map=gt_map, pre_map=pre_map, write_color=write_color, scene_counts=scene_counts)
+
     def epoch(self, batch_size, seed, shuffle=True, ragged='pad', rank=None, world=None):
         """An iterable with ``demos._Epoch``'s contract, ``((x, y, item, ref[, region]), n_real, weight)`` -- ``region`` when a
         scene of the set has one, ``item`` a CPU int64 tensor, ``weight`` an ``EpochWeight`` -- over the batches, pads and

@@ -474,6 +474,24 @@ typedef struct fcd_scene_desc {
 int fcd_scene_set_cut(const fcd_scene_desc* descs, int S, int sample_type, int C, const int32_t* table, int T,
                       const int32_t* index, int n, int ph, int pw, const double* stats, float* x, float* y, float* ref_tiles,
                       float* region_tiles, float* valid, void* stream);
+/* fcd_scene_stitch for a batch whose tiles come from S resident scenes, in ONE launch -- the inference side of the set: the
+ * per-epoch test pass over several scenes (Demo_RSSS.py:399-447) and the final per-scene maps (Demo_RSSS.py:451-502), whose
+ * batches cross scene borders.  cmap: n*ph*pw floats.  descs, S, table, T, index: as for fcd_scene_set_cut; of a descriptor
+ * only ref, ref_type, H and W are read, the reference map through its own sample type (uint8 / uint16 / float32), ref == 0 =
+ * the scene has no reference.  density, color: ONE flat buffer of `total` floats each that holds the maps of all scenes end to
+ * end; map_off: device int64[S+1], scene s occupies [map_off[s], map_off[s+1]) and map_off[s+1] - map_off[s] == H_s*W_s (the
+ * caller makes the offsets from the grids the tile table was made from and validates them before their one upload).
+ * Per owned-centre pixel exactly fcd_scene_stitch's rules, above; a tile of a scene without a reference gets the
+ * write_color == 0 rule (1 where pre == pre1) and counts nothing.  scene_counts (optional): S*4 unsigned 64-bit integers owned
+ * by the caller, row s = the four cells of scene s in Evaluator.add_batch_map's order, ACCUMULATED across calls by integer
+ * atomics (runs are bit-identical); the overall confusion matrix is the sum of the rows.
+ * No item may own the same pixels twice among the n tiles (the caller rejects repeats): the result would depend on the order
+ * the workgroups arrive in.  An index outside [0,T), a scene outside [0,S), a map span that is not H*W or leaves `total`, or an
+ * owned rectangle outside its scene writes nothing and counts nothing. */
+int fcd_scene_set_stitch(const float* cmap, const fcd_scene_desc* descs, int S, const int32_t* table, int T,
+                         const int32_t* index, int n, int ph, int pw, int padx, int pady, float thresh, float gt0, float gt1,
+                         float pre0, float pre1, int write_color, const int64_t* map_off, int64_t total, float* density,
+                         float* color, unsigned long long* scene_counts, void* stream);
 /* Masked per-band moments of a resident scene pair over the read rectangles of a tile table (CommonFunc.Dataset_mean /
  * Dataset_std, CommonFunc.py:436-500).  A pixel is valid when the fp32 sum of the bands of scene_x, in band order, is
  * non-zero (a NaN sum is valid); the same mask serves both scenes; a pixel read by two tiles counts twice.  C <= 32.
